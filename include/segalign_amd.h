@@ -13,7 +13,8 @@
  *
  * Threading mirrors the reference: sa_seed_and_filter* may be called from many host threads concurrently; the
  * engine hands each call a (device, slot) token from a pool (reference: seed_filter_interface.cu:7-9 +
- * src/seed_filter.cu:699-706,798-803).  All other entry points are called from one thread at a time
+ * src/seed_filter.cu:699-706,798-803).  sa_gapped_extend takes a token from the same pool and may likewise be called from many
+ * host threads at once.  All other entry points are called from one thread at a time
  * (the reader lambda of src/main.cpp:601-737).
  */
 #ifndef SEGALIGN_AMD_H
@@ -329,6 +330,81 @@ size_t sa_extend_hits(const uint32_t* ref_query_pairs, size_t num_hits, int rev,
  * library-sort chain.  *out is malloc'ed (sa_free_segments); returns the number of records kept.  Held against rocThrust's own
  * stable_sort / unique_copy in tests/test_gpu_thrust_order.py (hazard H3: unique_copy = head flags on adjacent INPUT pairs). */
 size_t sa_order_hsps(const sa_segment_pair* in, size_t n, int rm, int path, sa_segment_pair** out);
+
+/* ---- gapped extension of HSP anchors (additive) ------------------------------------------------
+ *
+ * The gapped stage the reference hands to LASTZ (src/segment_printer.cpp:96-113), done on the device with semantics of this
+ * project's own.  They are NOT claimed to equal LASTZ's: LASTZ is not available to pin them to.  tests/cpp/gapped_check.c restates
+ * them serially and the tests hold every field of every raw record against it.
+ *
+ * Inputs: HSPs as sa_seed_and_filter* / sa_seed_calls return them (len = bases - 1) on strand `rev` of query buffer `buffer`, the
+ * resident target block, the 8 x 8 sub_mat of sa_initialize_processor and the parameters below.  A gap of k bases costs O + k E.
+ *
+ * Anchor: a_r = ref_start + len / 2, a_q = query_start + len / 2 (integer division).  Two one-sided extensions:
+ *   right: X[i] = T[a_r + i],     Y[j] = Q[a_q + j]      (the anchor base belongs to the right side)
+ *   left:  X[i] = T[a_r - 1 - i], Y[j] = Q[a_q - 1 - j]
+ * Recurrence per side (Gotoh), cells (i, j) indexed by bases consumed:
+ *   H(0,0) = 0;  E(i,j) = max(E(i,j-1), H(i,j-1) - O) - E_ext;  F(i,j) = max(F(i-1,j), H(i-1,j) - O) - E_ext;
+ *   M(i,j) = H(i-1,j-1) + sub_mat[X[i-1] * 8 + Y[j-1]];  H = max(M, E, F).  A dead cell has H = E = F = -infinity.
+ * Dead cells: (i >= 1, .) when X[i-1] is a separator, (., j >= 1) when Y[j-1] is one -- code 7 (E_NT, the '&' between records) or any
+ *   position outside the block -- so no alignment crosses a record boundary, not even by a gap; and every cell with i > max_extent or
+ *   j > max_extent.
+ * Y-drop: antidiagonals d = i + j = 1, 2, ... in order.  B_d = best H over the live cells of antidiagonals < d (B_0 = 0).  A cell on d
+ *   is live if it is not dead, its H is finite and H >= B_d - ydrop; a cell that is not live takes part in no later cell (its H, E
+ *   and F are -infinity).  A side ends after two consecutive antidiagonals without a live cell (one empty antidiagonal can still be
+ *   crossed by M).
+ * Band cap: a side ends before d, flagged SA_GAPPED_BAND_CAP, if the live cells of d span more than max_band values of i -- or if the
+ *   cells of d next to a live cell of d - 1 or diagonal to one of d - 2 span more than max_band + 1 values of i (possible only when
+ *   the live cells of two consecutive antidiagonals lie apart).  A side with a live cell at i = max_extent or j = max_extent is
+ *   flagged SA_GAPPED_EXTENT_CAP.
+ * Best cell: the first cell reaching the maximum -- in antidiagonal order, then smallest i (strict >); (0, 0) with score 0 starts.
+ * Record: score = best_left + best_right; target extent [a_r - i_L, a_r + i_R), query extent [a_q - j_L, a_q + j_R) (strand `rev`
+ *   coordinates); flags of both sides OR-ed; cells = the live cells of both sides, each side's (0, 0) included.
+ * Selection (raw = 0): (1) keep score >= gappedthresh; (2) of records with identical (ref_start, ref_end, query_start, query_end)
+ *   keep the highest score, on a tie the lowest hsp_index; (3) order by (query_start, ref_start, query_end, ref_end, -score,
+ *   hsp_index).  raw != 0: one record per input HSP in input order, no threshold, no de-duplication.
+ * Not done: traceback / CIGAR / MAF, LASTZ's skipping of anchors inside earlier alignments (redundant anchors are extended and
+ *   removed by rule (2)), bit-identity with LASTZ. */
+#define SA_GAPPED_EXTENT_CAP 1u /* a side reached max_extent bases */
+#define SA_GAPPED_BAND_CAP 2u   /* a side ended at the band cap */
+
+typedef struct sa_gapped_params {
+    int32_t gap_open;     /* O, default 400; 0 .. 1 << 20 */
+    int32_t gap_extend;   /* E_ext, default 30; 0 .. 1 << 20 */
+    int32_t ydrop;        /* default 9430; 0 .. 1 << 28 */
+    int32_t gappedthresh; /* selection threshold (the host's default is hspthresh, src/main.cpp:182-183) */
+    uint32_t max_extent;  /* bases per side; 0 = 65536; at most 1 << 18 */
+    uint32_t max_band;    /* i values the live cells of one antidiagonal may span; 0 = 1024; at most 2048 */
+} sa_gapped_params;
+
+typedef struct sa_gapped_alignment { /* 32 bytes */
+    uint32_t ref_start, ref_end;     /* [ref_start, ref_end) in the target block */
+    uint32_t query_start, query_end; /* [query_start, query_end) in strand `rev` of the query block */
+    int32_t score;
+    uint32_t hsp_index;              /* position of the HSP in the input */
+    uint32_t flags;                  /* SA_GAPPED_* */
+    uint32_t cells;                  /* live cells of both sides */
+} sa_gapped_alignment;
+#ifdef __cplusplus
+static_assert(sizeof(sa_gapped_alignment) == 32, "sa_gapped_alignment is 32 bytes");
+#else
+_Static_assert(sizeof(sa_gapped_alignment) == 32, "sa_gapped_alignment is 32 bytes");
+#endif
+
+typedef struct sa_gapped_stats {
+    uint64_t anchors;       /* HSPs extended */
+    uint64_t cells;         /* live cells, summed over the HSPs */
+    uint64_t extent_capped; /* HSPs with SA_GAPPED_EXTENT_CAP */
+    uint64_t band_capped;   /* HSPs with SA_GAPPED_BAND_CAP */
+    uint64_t returned;      /* records returned */
+    double kernel_ms;       /* device time of the extension launches */
+} sa_gapped_stats;
+
+/* Returns the number of records in *out (malloc-ed, release with sa_free_gapped; NULL when 0).  p: NULL = the defaults, with
+ * gappedthresh = the hspthresh of sa_initialize_processor.  stats: nullable. */
+size_t sa_gapped_extend(const sa_segment_pair* hsps, size_t n, int rev, uint32_t buffer, const sa_gapped_params* p, int raw,
+                        sa_gapped_alignment** out, sa_gapped_stats* stats);
+void sa_free_gapped(sa_gapped_alignment* p);
 
 const char* sa_version(void);
 

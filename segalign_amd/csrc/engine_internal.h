@@ -11,6 +11,7 @@
 //   api_setup.hip      InitializeInterface / InitializeProcessor / Shutdown, target + query upload, GenerateSeedPosTable
 //   api_calls.hip      SeedAndFilter and its additive forms (range, chunks, interval, call lists), ExtendHits, DeviceMakeSeeds
 //   api_rm.hip         repeat-masker entries and the device-side coverage post-processing
+//   api_gapped.hip     sa_gapped_extend: gapped y-drop extension of HSP anchors (kernel: gapped.hip)
 //   api_introspect.hip statistics, lookup mode, copies of device state for the tests
 #pragma once
 #include <hip/hip_runtime.h>
@@ -333,6 +334,7 @@ struct Slot {
     JoinChunk* h_jplan = nullptr;     // pinned
     uint32_t jq_chunk = 0;            // chunk size of the running key-ordered call
     WorkRegion work;                  // this slot's share of the device's work arena
+    DevBuf<uint8_t> gapped;           // sa_gapped_extend: a batch's HSPs and its per-side results (api_gapped.hip)
 };
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -88,6 +88,7 @@ void slot_destroy(Slot& s) {
     s.flag_prefix.release("flag_prefix"); s.prefix.release("prefix"); s.scan_temp.release("scan_temp");
     s.sort_temp.release("sort_temp"); s.unique_temp.release("unique_temp"); s.hits.release("hits"); s.recA.release("recA"); s.recB.release("recB");
     s.out16.release("out16");
+    s.gapped.release("gapped");
     s.cand_list.release("candidate list");
     s.l2_list.release("second-level list");
     s.audit.release("audit list");

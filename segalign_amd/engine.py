@@ -38,11 +38,27 @@ C_ABI_SYMBOLS = [
     "sa_seed_interval", "sa_seed_and_filter_chunks", "sa_max_chunks_per_call", "sa_get_chunks_per_call", "sa_extend_hits", "sa_order_hsps",
     "sa_get_lookup_mode", "sa_get_neighbourhood_entries",
     "sa_seed_calls", "sa_count_call_hits", "sa_count_chunk_hits", "sa_get_wga_chunk", "sa_release_arena", "sa_set_option", "sa_reset_option", "sa_get_option", "sa_option_count", "sa_option_name", "sa_get_audit",
+    "sa_gapped_extend", "sa_free_gapped",
 ]
 IVL_DTYPE = np.dtype([("query_start", "<u4"), ("len", "<u4")])  # struct Segment, repeat_masker_src/graph.h:32-35
 STRAND_PLUS, STRAND_MINUS, STRAND_BOTH = 1, 2, 3
 PATH_LIST_REGROWN, PATH_DEDUP_FALLBACK, PATH_CHAIN_BUCKET_OVERFLOW, PATH_CHAIN_SLICED, PATH_HEAD_BITS_REGROWN, PATH_GENERAL_FALLBACK = 1, 2, 4, 8, 16, 32
 PATH_KEY_ORDERED = 64
+
+
+GAPPED_DTYPE = np.dtype([("ref_start", "<u4"), ("ref_end", "<u4"), ("query_start", "<u4"), ("query_end", "<u4"), ("score", "<i4"),
+                         ("hsp_index", "<u4"), ("flags", "<u4"), ("cells", "<u4")])  # sa_gapped_alignment
+GAPPED_EXTENT_CAP, GAPPED_BAND_CAP = 1, 2
+
+
+class GappedParams(C.Structure):
+    _fields_ = [("gap_open", C.c_int32), ("gap_extend", C.c_int32), ("ydrop", C.c_int32), ("gappedthresh", C.c_int32),
+                ("max_extent", C.c_uint32), ("max_band", C.c_uint32)]
+
+
+class GappedStats(C.Structure):
+    _fields_ = [("anchors", C.c_uint64), ("cells", C.c_uint64), ("extent_capped", C.c_uint64), ("band_capped", C.c_uint64),
+                ("returned", C.c_uint64), ("kernel_ms", C.c_double)]
 
 
 class CallStats(C.Structure):
@@ -137,6 +153,10 @@ def lib():
     L.sa_option_name.argtypes = [C.c_int, C.POINTER(C.c_int)]
     L.sa_get_audit.restype = C.c_size_t
     L.sa_get_audit.argtypes = [C.c_void_p, C.c_size_t]
+    L.sa_gapped_extend.restype = C.c_size_t
+    L.sa_gapped_extend.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(GappedParams), C.c_int, C.POINTER(C.c_void_p),
+                                   C.POINTER(GappedStats)]
+    L.sa_free_gapped.argtypes = [C.c_void_p]
     _lib = L
     return L
 
@@ -310,6 +330,24 @@ def ExtendHits(hits, rev, buffer):
     out = C.c_void_p()
     n = lib().sa_extend_hits(h.ctypes.data, h.shape[0], int(bool(rev)), buffer, C.byref(out))
     return _take(n, out)[1:]
+
+
+def GappedExtend(hsps, rev, buffer, gap_open=400, gap_extend=30, ydrop=9430, gappedthresh=3000, max_extent=0, max_band=0, raw=False):
+    """Gapped y-drop extension of HSP anchors on the device (sa_gapped_extend; contract in include/segalign_amd.h).
+    hsps: SEG_DTYPE records (len = bases - 1) on strand `rev` of query `buffer`.  -> (GAPPED_DTYPE array, stats dict).
+    raw: one record per HSP in input order; otherwise threshold, one record per extent, output order."""
+    h = np.ascontiguousarray(hsps, dtype=SEG_DTYPE)
+    p = GappedParams(int(gap_open), int(gap_extend), int(ydrop), int(gappedthresh), int(max_extent), int(max_band))
+    out = C.c_void_p()
+    st = GappedStats()
+    n = lib().sa_gapped_extend(h.ctypes.data if h.size else None, h.size, int(bool(rev)), buffer, C.byref(p), int(bool(raw)),
+                               C.byref(out), C.byref(st))
+    recs = np.zeros(0, dtype=GAPPED_DTYPE)
+    if n and out.value:
+        recs = np.frombuffer((C.c_char * (n * GAPPED_DTYPE.itemsize)).from_address(out.value), dtype=GAPPED_DTYPE).copy()
+    if out.value:
+        lib().sa_free_gapped(out)
+    return recs, {k: getattr(st, k) for k, _ in GappedStats._fields_}
 
 
 def SeedInterval(start, end, q_len, strands=STRAND_BOTH, buffer=0, threads=2):

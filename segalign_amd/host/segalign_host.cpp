@@ -38,6 +38,8 @@ struct Config {  // src/graph.h:32-76 with the defaults of src/main.cpp:61-124
     std::string strand = "both", seed_shape = "12of19", ambiguous = "", scoring_file = "", output_format = "maf-";
     uint32_t step = 1;
     bool transition = true, noentropy = false, gapped = true, notrivial = false, debug = false, host_seeding = false;
+    bool gpu_gapped = false;  // --gpu_gapped: a .gapped file next to every .segments file (sa_gapped_extend)
+    int gap_open = 400, gap_extend = 30;
     int xdrop = 910, hspthresh = 3000, ydrop = 9430, gappedthresh = -1;
     uint32_t wga_chunk = 250000, lastz_interval = 10000000, seq_block_size = 500000000;
     int num_gpu = -1, num_threads = 0;
@@ -209,7 +211,7 @@ static std::mutex io_lock;
 
 // segment_printer_body::operator(), src/segment_printer.cpp:11-173
 static void print_segments(int r_block_index, int q_block_index, size_t r_block_start, size_t q_block_start, uint32_t index,
-                           const Hsps& h) {
+                           const Hsps& h, uint32_t buffer) {
     for (int rev = 0; rev < 2; rev++) {
         const std::vector<sa_segment_pair>& v = rev ? h.rc : h.fw;
         if (v.empty()) continue;
@@ -230,6 +232,25 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
         if (!rev) for (size_t i = 0; i < v.size(); i++) emit(v[i]);
         else for (size_t i = v.size(); i-- > 0;) emit(v[i]);  // :130: reverse vector order on the minus strand
         fclose(f);
+        if (cfg.gpu_gapped) {  // the gapped extension of the same HSPs on the device: [start, end) extents printed like the segments
+            sa_gapped_params gp = {cfg.gap_open, cfg.gap_extend, cfg.ydrop, cfg.gappedthresh, 0, 0};
+            sa_gapped_alignment* al = nullptr;
+            const size_t na = sa_gapped_extend(v.data(), v.size(), rev, buffer, &gp, 0, &al, nullptr);
+            std::string gname = base + ".gapped";
+            FILE* g = fopen((cfg.outdir + "/" + gname).c_str(), "w");
+            if (!g) die(7, "cant open file: %s", gname.c_str());
+            auto emit_gapped = [&](const sa_gapped_alignment& a) {
+                size_t r0 = a.ref_start + r_block_start, q0 = a.query_start + q_block_start;
+                size_t ri = chr_of(R.chr_start, r0), qi = chr_of(qs, q0);
+                fprintf(g, "%s\t%zu\t%zu\t%s\t%zu\t%zu\t%c\t%d\n", R.chr_name[ri].c_str(), r0 + 1 - R.chr_start[ri],
+                        a.ref_end + r_block_start - R.chr_start[ri], qn[qi].c_str(), q0 + 1 - qs[qi], a.query_end + q_block_start - qs[qi],
+                        rev ? '-' : '+', a.score);
+            };
+            if (!rev) for (size_t i = 0; i < na; i++) emit_gapped(al[i]);
+            else for (size_t i = na; i-- > 0;) emit_gapped(al[i]);  // reverse order on the minus strand, as the segments
+            fclose(g);
+            sa_free_gapped(al);
+        }
         if (cfg.gapped) {  // :96-113 / :151-168
             std::string cmd = "lastz " + cfg.data_folder + "ref.2bit[nameparse=darkspace][multiple][subset=ref_block" +
                               std::to_string(r_block_index) + ".name] " + cfg.data_folder +
@@ -253,7 +274,8 @@ static void usage() {
             "  --xdrop=N --hspthresh=N --noentropy --nogapped --ydrop=N --gappedthresh=N --notrivial --format=F\n"
             "  --ambiguous=x|n|iupac[,reward,penalty] --scoring=FILE\n"
             "  --wga_chunk=N --lastz_interval=N --seq_block_size=N --num_gpu=N --num_threads=N --outdir=DIR\n"
-            "  --host-seeding (build seed vectors on the host like src/seeder.cpp) --debug\n");
+            "  --host-seeding (build seed vectors on the host like src/seeder.cpp) --debug\n"
+            "  --gpu_gapped [--gap=O,E] (gapped y-drop extension on the GPU: a .gapped file next to each .segments file)\n");
 }
 
 int main(int argc, char** argv) {
@@ -286,6 +308,10 @@ int main(int argc, char** argv) {
         else if (opt(a, "--outdir", v)) cfg.outdir = v;
         else if (!strcmp(a, "--host-seeding")) cfg.host_seeding = true;
         else if (!strcmp(a, "--debug")) cfg.debug = true;
+        else if (!strcmp(a, "--gpu_gapped")) cfg.gpu_gapped = true;
+        else if (opt(a, "--gap", v)) {
+            if (sscanf(v.c_str(), "%d,%d", &cfg.gap_open, &cfg.gap_extend) != 2) { fprintf(stderr, "bad --gap=%s\n", v.c_str()); return 1; }
+        }
         else { fprintf(stderr, "unknown option %s\n", a); usage(); return 1; }
     }
     if (pos.size() < 2) {
@@ -362,7 +388,7 @@ int main(int argc, char** argv) {
                             ivs[i].start, ivs[i].end, buffer);                                                   // seeder.cpp:45
                     Hsps h;
                     seed_interval(Q.block_start[qb], q_len, ivs[i], buffer, h);
-                    print_segments((int)rb, (int)qb, R.block_start[rb], Q.block_start[qb], (uint32_t)i + 1, h);
+                    print_segments((int)rb, (int)qb, R.block_start[rb], Q.block_start[qb], (uint32_t)i + 1, h, buffer);
                 }
             };
             std::vector<std::thread> pool;
