@@ -232,6 +232,8 @@ int sa_max_hits_for_mem(uint64_t total_global_mem);
  *   debug             1: table-build timings on stderr; 2: + synchronise after every kernel scope and name it (fault localisation)
  *   seed_upload       how sa_seed_and_filter brings the host seed vector over: 0 copy into a pinned staging buffer + DMA (default),
  *                     1 hipMemcpyAsync from the pageable vector (the runtime stages it), 2 hipHostRegister the vector + DMA
+ *   gapped_trace_mb   MiB of trace area one sa_gapped_align batch packs its traced sides into (default 1024; a side that needs more
+ *                     runs in a batch of its own and grows the slot's buffer to fit).  Each slot keeps its buffer until shutdown
  * Launch geometry (defaults are the measured optima, tools/sweep_*.sh)
  *   fin_batch, bufs_per_wave, long_cap, long_blocks, max_waves, packed_waves, l2_blocks, ctx_waves, ctx_threads,
  *   chain_sort_threads, chain_sort_blocks, chain_group_max (candidates a chain workgroup sorts in LDS at a time), chain_bucket_target
@@ -363,8 +365,8 @@ size_t sa_order_hsps(const sa_segment_pair* in, size_t n, int rm, int path, sa_s
  * Selection (raw = 0): (1) keep score >= gappedthresh; (2) of records with identical (ref_start, ref_end, query_start, query_end)
  *   keep the highest score, on a tie the lowest hsp_index; (3) order by (query_start, ref_start, query_end, ref_end, -score,
  *   hsp_index).  raw != 0: one record per input HSP in input order, no threshold, no de-duplication.
- * Not done: traceback / CIGAR / MAF, LASTZ's skipping of anchors inside earlier alignments (redundant anchors are extended and
- *   removed by rule (2)), bit-identity with LASTZ. */
+ * Not done: LASTZ's skipping of anchors inside earlier alignments (redundant anchors are extended and removed by rule (2)),
+ *   bit-identity with LASTZ.  The alignment path of each record (traceback) is sa_gapped_align's, below. */
 #define SA_GAPPED_EXTENT_CAP 1u /* a side reached max_extent bases */
 #define SA_GAPPED_BAND_CAP 2u   /* a side ended at the band cap */
 
@@ -405,6 +407,72 @@ typedef struct sa_gapped_stats {
 size_t sa_gapped_extend(const sa_segment_pair* hsps, size_t n, int rev, uint32_t buffer, const sa_gapped_params* p, int raw,
                         sa_gapped_alignment** out, sa_gapped_stats* stats);
 void sa_free_gapped(sa_gapped_alignment* p);
+
+/* ---- gapped alignment paths (additive) ----------------------------------------------------------
+ *
+ * sa_gapped_align does exactly what sa_gapped_extend does -- the same records in the same order for the same arguments, raw and
+ * selection mode alike -- and also returns the alignment path of every record.  tests/cpp/gapped_trace_check.c restates it serially.
+ *
+ * Path of one side: from its best cell (best_i, best_j) back to the anchor cell (0, 0) through the recurrence above, in states
+ * H, E, F, with fixed tie rules:
+ *   state H at (i, j): take M if H == M (i, j >= 1), otherwise E if H == E, otherwise F;
+ *   state E at (i, j): op I (query base Y[j-1] against a gap); extend (state E at (i, j-1)) if E(i, j-1) > H(i, j-1) - O, otherwise
+ *     open (state H at (i, j-1)) -- a tie opens;
+ *   state F at (i, j): op D (target base X[i-1] against a gap); the same rule with (i-1, j);
+ *   M: op M (an aligned pair), state H at (i-1, j-1).
+ * The path stays on live cells.  Invariant: the value of the current state at the current cell is finite (> -infinity / 2).  It
+ * holds at the best cell (a live cell: H finite).  H finite and H == M: M finite, so H(i-1, j-1) is finite; H == E or F: that value is
+ * finite.  E(i, j) finite: E(i, j) + E_ext = max(E(i, j-1), H(i, j-1) - O) is finite (a max reaching only -infinity clamps E(i, j) to
+ * -infinity), and the rule picks the argument that attains it (on a tie H(i, j-1) - O, which equals the max) -- so the next state's
+ * value is finite; F likewise.  A cell that is not live (dead, pruned by the y-drop or outside the candidate range) has H = E = F =
+ * -infinity, so every cell the path visits is live: no op consumes a separator, a base outside the block or a pruned cell.
+ *
+ * Ops: uint32 (run_length << 2) | op, op SA_GAPPED_OP_M / _I / _D, run-length form inside each side (no zero runs, no two adjacent
+ * runs with the same op).  A record's ops are in genome order: the left side's runs (its walk order is genome order), then the right
+ * side's runs (walk order reversed).  The two sides are not merged at the anchor: n_left / n_right split them, and gap runs meeting
+ * at the anchor are two runs, charged two opens, as the extension charged them.  With O > 0 every run of I or D is exactly one
+ * opened gap of the recurrence (a tie opens, and H == E at the cell an E run opened from would have made it extend); with O = 0 a
+ * run may hold several back-to-back opens, which cost nothing.  Re-scoring each side: sum of sub_mat over its M pairs minus
+ * (O + length x E_ext) per gap run equals that side's best, and the two sides' scores sum to score.  The left side's ops consume
+ * [ref_start, a_r) and [query_start, a_q), the right side's [a_r, ref_end) and [a_q, query_end). */
+#define SA_GAPPED_OP_M 0u /* aligned pair: one target and one query base */
+#define SA_GAPPED_OP_I 1u /* query base against a gap */
+#define SA_GAPPED_OP_D 2u /* target base against a gap */
+
+typedef struct sa_gapped_path { /* 32 bytes, one per record */
+    uint64_t op_offset;         /* index of the record's first op in *ops */
+    uint32_t n_left, n_right;   /* runs of the left side, then of the right side */
+    uint32_t matches;           /* M pairs with equal codes < 4 */
+    uint32_t mismatches;        /* all other M pairs */
+    uint32_t gap_opens;         /* I and D runs of both sides */
+    uint32_t gap_bases;         /* bases in those runs */
+} sa_gapped_path;
+#ifdef __cplusplus
+static_assert(sizeof(sa_gapped_path) == 32, "sa_gapped_path is 32 bytes");
+#else
+_Static_assert(sizeof(sa_gapped_path) == 32, "sa_gapped_path is 32 bytes");
+#endif
+
+typedef struct sa_gapped_align_stats {
+    sa_gapped_stats extend; /* the extension's statistics, as sa_gapped_extend reports them */
+    double trace_ms;        /* device time of the trace sweeps */
+    double walk_ms;         /* device time of the path walks */
+    uint64_t trace_bytes;   /* trace bytes written, summed over the batches */
+    uint64_t trace_batches; /* batches the traced sides were packed into (option gapped_trace_mb) */
+} sa_gapped_align_stats;
+#ifdef __cplusplus
+static_assert(sizeof(sa_gapped_align_stats) == 80, "sa_gapped_align_stats is 80 bytes");
+#else
+_Static_assert(sizeof(sa_gapped_align_stats) == 80, "sa_gapped_align_stats is 80 bytes");
+#endif
+
+/* Returns the number of records.  *out, *paths (one per record) and *ops (*n_ops entries) are malloc-ed, released together with
+ * sa_free_gapped_align; each is NULL when it would be empty (n == 0, nothing selected, or no op at all).  Every other argument is
+ * sa_gapped_extend's.  Traced sides are packed into batches whose trace areas fit option gapped_trace_mb (a larger side runs alone
+ * and grows the slot's buffer to fit).  stats: nullable. */
+size_t sa_gapped_align(const sa_segment_pair* hsps, size_t n, int rev, uint32_t buffer, const sa_gapped_params* p, int raw,
+                       sa_gapped_alignment** out, sa_gapped_path** paths, uint32_t** ops, size_t* n_ops, sa_gapped_align_stats* stats);
+void sa_free_gapped_align(sa_gapped_alignment* out, sa_gapped_path* paths, uint32_t* ops);
 
 const char* sa_version(void);
 

@@ -11,7 +11,7 @@
 //   api_setup.hip      InitializeInterface / InitializeProcessor / Shutdown, target + query upload, GenerateSeedPosTable
 //   api_calls.hip      SeedAndFilter and its additive forms (range, chunks, interval, call lists), ExtendHits, DeviceMakeSeeds
 //   api_rm.hip         repeat-masker entries and the device-side coverage post-processing
-//   api_gapped.hip     sa_gapped_extend: gapped y-drop extension of HSP anchors (kernel: gapped.hip)
+//   api_gapped.hip     sa_gapped_extend / sa_gapped_align: gapped y-drop extension of HSP anchors and its paths (kernels: gapped.hip)
 //   api_introspect.hip statistics, lookup mode, copies of device state for the tests
 #pragma once
 #include <hip/hip_runtime.h>
@@ -240,6 +240,7 @@ int prof_id(const char* name);
 // per-device state
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int MAX_SLOTS_PER_DEVICE = 8;
+extern int64_t g_gapped_trace_mb;  // option gapped_trace_mb: MiB of trace area per sa_gapped_align batch
 extern uint32_t SPEC_RECS;        // records of the speculative output copy (256 KB); option spec_recs (tests)
 extern uint32_t g_dedup_seg_max;  // option dedup_seg_max: records per segment the LDS chain accepts (0 = its LDS capacity; tests)
 constexpr int SA_MAX_CHUNKS = 256;  // chunks one multi-chunk call may carry: 2 reference iterations each = MAX_SEGS segments
@@ -335,6 +336,7 @@ struct Slot {
     uint32_t jq_chunk = 0;            // chunk size of the running key-ordered call
     WorkRegion work;                  // this slot's share of the device's work arena
     DevBuf<uint8_t> gapped;           // sa_gapped_extend: a batch's HSPs and its per-side results (api_gapped.hip)
+    DevBuf<uint8_t> gapped_trace;     // sa_gapped_align: a batch's side tasks, walk results, op areas and trace areas (api_gapped.hip)
 };
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -31,4 +31,28 @@ struct GappedArgs {
 int gapped_cells_per_lane(int max_band);  // K of the kernel instance a band needs (64 K >= max_band + 1); -1: too wide
 void launch_gapped(const GappedArgs& a, hipStream_t s);
 
+// ---- trace sweep and path walk (sa_gapped_align) ----
+struct TraceTask {  // one side to trace: a side whose best cell is not the anchor
+    uint32_t ar, aq;     // anchor (a_r, a_q)
+    int32_t dir;         // -1 left, +1 right
+    int32_t dstar;       // best_i + best_j of the side (pass 1): the trace covers antidiagonals 1 .. dstar
+    int32_t best_i, best_j;
+    uint64_t trace_off;  // byte offset of the side's trace area in the batch's trace buffer (256-aligned)
+    uint64_t ops_off;    // first entry of the side's op area (dstar entries) in the batch's op buffer
+};
+
+struct TraceOut {  // what the walk of one side found
+    uint32_t n_runs;  // run-length ops written, in walk order (best cell -> anchor)
+    uint32_t matches, mismatches, gap_opens, gap_bases;
+    uint32_t err;     // != 0: the walk left the traced cells (a broken invariant; the host aborts)
+    uint32_t pad[2];
+};
+
+// Trace area of one side: dstar rows of 64 x ceil(K / 8) dwords (row d - 1 = antidiagonal d; dword w * 64 + l holds the 4-bit codes of
+// lane l's cells 8 w .. 8 w + 7), then the window base of antidiagonals 0 .. dstar as int32.  Rounded up to 256 bytes.
+size_t gapped_trace_bytes(int max_band, int dstar);
+void launch_gapped_trace(const GappedArgs& a, const TraceTask* tasks, uint32_t n, uint8_t* area, hipStream_t s);
+void launch_gapped_walk(const GappedArgs& a, const TraceTask* tasks, uint32_t n, const uint8_t* area, uint32_t* ops, TraceOut* out,
+                        hipStream_t s);
+
 }  // namespace sa

@@ -13,6 +13,10 @@
 //   * per antidiagonal: a ballot gives the live range (band cap, next step's candidate range), a wave max-reduction the best cell.
 //
 // Values are int32 clamped at NEG (minus infinity); finite values stay above NEG / 2 under the parameter limits of the C-ABI.
+//
+// sa_gapped_align adds two kernels: the TRACE instance of the same sweep, which stops at the side's best antidiagonal d*
+// and stores 4 bits per cell (H source, E extend, F extend) plus the window base of every antidiagonal, and a walk kernel that
+// follows those bits from the best cell back to the anchor, 64 antidiagonals at a time staged in LDS.
 #include "gapped.h"
 
 namespace sa {
@@ -103,9 +107,14 @@ struct Stream {
     }
 };
 
-template <int K>
-__device__ void gapped_side(const GappedArgs& a, const int* __restrict__ sub, const Seq& X, const Seq& Y, GappedSide* out) {
+// TRACE = false: the extension (pass 1), result in *out.  TRACE = true: the same sweep over antidiagonals 1 .. dstar only, writing the
+// trace area of gapped.h (4-bit cell codes: bits 0-1 the source of H -- 0 M, 1 E, 2 F, by the tie rules of the contract --, bit 2 E
+// extends, bit 3 F extends) and nothing else.
+template <int K, bool TRACE>
+__device__ void gapped_side(const GappedArgs& a, const int* __restrict__ sub, const Seq& X, const Seq& Y, GappedSide* out,
+                            uint32_t* __restrict__ trace, int dstar) {
     constexpr int W = 64 * K;
+    constexpr int NW = (K + 7) / 8;  // trace dwords per lane per antidiagonal
     const int lane = threadIdx.x & 63;
     const int O = a.gap_open, Ext = a.gap_extend, ydrop = a.ydrop, maxe = a.max_extent, maxband = a.max_band;
     int H1[K], E1[K], F1[K], H2[K], xc[K], yc[K];
@@ -125,7 +134,15 @@ __device__ void gapped_side(const GappedArgs& a, const int* __restrict__ sub, co
     int lo1 = 0, hi1 = 0, lo2 = 1, hi2 = 0;  // their live ranges (lo > hi: none)
     int best = 0, best_i = 0, best_j = 0;
     unsigned cnt = 0, ext = 0, flags = 0;
+    int* wbase = nullptr;
+    if constexpr (TRACE) {
+        wbase = (int*)(trace + (size_t)dstar * 64 * NW);
+        if (lane == 0) wbase[0] = 0;
+    }
     for (int d = 1;; d++) {
+        if constexpr (TRACE) {
+            if (d > dstar) break;  // the best cell's antidiagonal is traced: the sweep up to it is pass 1's, step for step
+        }
         const bool e1 = lo1 > hi1, e2 = lo2 > hi2;
         if (e1 && e2) break;  // two consecutive antidiagonals without a live cell
         int lo = 0x7fffffff, hi = -0x7fffffff;
@@ -161,6 +178,9 @@ __device__ void gapped_side(const GappedArgs& a, const int* __restrict__ sub, co
         const int floor_ = best - ydrop;
         int lbest = NEG, lbest_s = 0, llo_s = -1, lhi_s = -1;
         unsigned lcnt = 0, lext = 0;
+        uint32_t pk[NW];
+#pragma unroll
+        for (int k = 0; k < NW; k++) pk[k] = 0;
 #pragma unroll
         for (int s = 0; s < K; s++) {
             const int i = w + lane * K + s, j = d - i;
@@ -169,6 +189,11 @@ __device__ void gapped_side(const GappedArgs& a, const int* __restrict__ sub, co
             const int f = max(max(Ff[s], Fh[s] - O) - Ext, NEG);
             const int m = (i >= 1 && j >= 1) ? max(Mh[s] + sub[xc[s] * 8 + yc[s]], NEG) : NEG;
             const int h = max(m, max(e, f));
+            if constexpr (TRACE) {  // (the codes of cells that are not live are never read)
+                const uint32_t src = m == h ? 0u : (e == h ? 1u : 2u);
+                const uint32_t eb = Ee[s] > Eh[s] - O, fb = Ff[s] > Fh[s] - O;
+                pk[s >> 3] |= (src | eb << 2 | fb << 3) << (4 * (s & 7));
+            }
             const bool live = !dead && h > NEG / 2 && h >= floor_;
             H2[s] = H1[s];
             H1[s] = live ? h : NEG;
@@ -181,6 +206,12 @@ __device__ void gapped_side(const GappedArgs& a, const int* __restrict__ sub, co
                 if (h > lbest) { lbest = h; lbest_s = s; }
                 if (i == maxe || j == maxe) lext = 1;
             }
+        }
+        if constexpr (TRACE) {
+            uint32_t* row = trace + (size_t)(d - 1) * 64 * NW;
+#pragma unroll
+            for (int k = 0; k < NW; k++) row[k * 64 + lane] = pk[k];
+            if (lane == 0) wbase[d] = w;
         }
         const unsigned long long mask = __ballot(llo_s >= 0);
         int nlo = 1, nhi = 0;
@@ -204,6 +235,7 @@ __device__ void gapped_side(const GappedArgs& a, const int* __restrict__ sub, co
         lo2 = lo1; hi2 = hi1;
         lo1 = nlo; hi1 = nhi;
     }
+    if constexpr (TRACE) return;
     const unsigned cells = wave_sum(cnt) + 1;  // + the anchor cell (0, 0)
     if (wave_or(ext)) flags |= SA_GAPPED_EXTENT_CAP;
     if (lane == 0) {
@@ -227,7 +259,133 @@ __global__ __launch_bounds__(256) void gapped_kernel(GappedArgs a) {
     const int dir = (task & 1) ? 1 : -1;
     const Seq X = {a.ref, (long long)a.ref_len, ar, dir};
     const Seq Y = {a.query, (long long)a.query_len, aq, dir};
-    gapped_side<K>(a, s_sub, X, Y, a.out + task);
+    gapped_side<K, false>(a, s_sub, X, Y, a.out + task, nullptr, 0);
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void gapped_trace_kernel(GappedArgs a, const TraceTask* __restrict__ tasks, uint32_t n, uint8_t* area) {
+    __shared__ int s_sub[64];
+    if (threadIdx.x < 64) s_sub[threadIdx.x] = a.sub_mat[threadIdx.x];
+    __syncthreads();
+    const uint32_t task = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (task >= n) return;
+    const TraceTask t = tasks[task];
+    const Seq X = {a.ref, (long long)a.ref_len, (long long)t.ar, t.dir};
+    const Seq Y = {a.query, (long long)a.query_len, (long long)t.aq, t.dir};
+    gapped_side<K, true>(a, s_sub, X, Y, nullptr, (uint32_t*)(area + t.trace_off), t.dstar);
+}
+
+// One wave per traced side.  The walk state (cell, H / E / F) is wave-uniform.  Every 64 antidiagonals the wave stages the codes of
+// the region the path can reach next -- antidiagonals d0 .. d0 - 63, target bases i0 - 63 .. i0 (each step lowers d by 1 or 2 and i
+// by at most as much) -- into LDS, one cell per lane and antidiagonal, all loads independent of one another; the walk then reads LDS
+// only.  The M pairs of a stage are matched against the codes afterwards, one pair per lane.
+template <int K>
+__global__ __launch_bounds__(256) void gapped_walk_kernel(GappedArgs a, const TraceTask* __restrict__ tasks, uint32_t n,
+                                                         const uint8_t* __restrict__ area, uint32_t* __restrict__ ops,
+                                                         TraceOut* __restrict__ out) {
+    constexpr int W = 64 * K, NW = (K + 7) / 8;
+    __shared__ uint8_t s_code[4][64][64];  // [wave][antidiagonal d0 - r][cell i0 - 63 + c]
+    __shared__ int s_mi[4][64], s_mj[4][64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t task = blockIdx.x * 4 + wave;
+    if (task >= n) return;
+    const TraceTask t = tasks[task];
+    const uint32_t* tr = (const uint32_t*)(area + t.trace_off);
+    const int* wbase = (const int*)(tr + (size_t)t.dstar * 64 * NW);
+    uint32_t* o = ops + t.ops_off;
+    const Seq X = {a.ref, (long long)a.ref_len, (long long)t.ar, t.dir};
+    const Seq Y = {a.query, (long long)a.query_len, (long long)t.aq, t.dir};
+    int i = t.best_i, j = t.best_j, st = 0;  // st: 0 H, 1 E, 2 F
+    int cur = -1;
+    uint32_t len = 0, nr = 0, opens = 0, gapb = 0, matches = 0, mism = 0, err = 0;
+    auto emit = [&](int op) {
+        if (op == cur) { len++; return; }
+        if (len) {
+            if (nr >= (uint32_t)t.dstar) { err = 1; return; }
+            if (lane == 0) o[nr] = len << 2 | (uint32_t)cur;
+            nr++;
+            if (cur != (int)SA_GAPPED_OP_M) { opens++; gapb += len; }
+        }
+        cur = op;
+        len = 1;
+    };
+    while (!err && i + j > 0) {
+        const int d0 = i + j, ib = i - 63;
+        const int nd = min(64, d0);  // antidiagonals d0 .. d0 - nd + 1, all >= 1
+        const int wl = lane < nd ? wbase[d0 - lane] : 0;
+#pragma unroll 16
+        for (int r = 0; r < 64; r++) {
+            const int w = __shfl(wl, r);
+            const int dd = d0 - r, ii = ib + lane, slot = ii - w;
+            uint32_t code = 0;  // cells the path cannot reach: never read
+            if (r < nd && ii >= 0 && dd - ii >= 0 && slot >= 0 && slot < W) {
+                const int l = slot / K, s = slot - l * K;
+                code = (tr[(size_t)(dd - 1) * 64 * NW + (s >> 3) * 64 + l] >> (4 * (s & 7))) & 15u;
+            }
+            s_code[wave][r][lane] = (uint8_t)code;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        int nm = 0;
+        while (i + j > 0 && d0 - (i + j) < nd) {
+            const int r = d0 - (i + j), c = i - ib;
+            if (i < 0 || j < 0 || c < 0 || c > 63 || nm >= 64) { err = 2; break; }
+            const uint32_t code = s_code[wave][r][c];
+            if (st == 0) {
+                const uint32_t src = code & 3u;
+                if (src == 0) {
+                    emit(SA_GAPPED_OP_M);
+                    s_mi[wave][nm] = i;
+                    s_mj[wave][nm] = j;
+                    nm++;
+                    i--;
+                    j--;
+                } else if (src == 3) {
+                    err = 3;
+                    break;
+                } else {
+                    st = (int)src;
+                }
+            } else if (st == 1) {
+                emit(SA_GAPPED_OP_I);
+                st = (code >> 2) & 1u ? 1 : 0;
+                j--;
+            } else {
+                emit(SA_GAPPED_OP_D);
+                st = (code >> 3) & 1u ? 2 : 0;
+                i--;
+            }
+            if (err) break;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        bool match = false;
+        if (lane < nm) {
+            const int x = X.code(s_mi[wave][lane] - 1), y = Y.code(s_mj[wave][lane] - 1);
+            match = x == y && x < 4;
+        }
+        const uint32_t nmatch = (uint32_t)__popcll(__ballot(match));
+        matches += nmatch;
+        mism += (uint32_t)nm - nmatch;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    if (!err && (i != 0 || j != 0 || st != 0)) err = 4;
+    if (!err) emit(-1);  // flush the last run
+    if (lane == 0) {
+        TraceOut r;
+        r.n_runs = nr;
+        r.matches = matches;
+        r.mismatches = mism;
+        r.gap_opens = opens;
+        r.gap_bases = gapb;
+        r.err = err;
+        r.pad[0] = r.pad[1] = 0;
+        out[task] = r;
+    }
 }
 
 }  // namespace
@@ -236,6 +394,36 @@ int gapped_cells_per_lane(int max_band) {
     for (int k : {2, 4, 8, 17, 33})
         if (64 * k >= max_band + 1) return k;
     return -1;
+}
+
+size_t gapped_trace_bytes(int max_band, int dstar) {
+    const size_t nw = (size_t)(gapped_cells_per_lane(max_band) + 7) / 8;
+    return ((size_t)dstar * 64 * nw * 4 + ((size_t)dstar + 1) * 4 + 255) & ~(size_t)255;
+}
+
+void launch_gapped_trace(const GappedArgs& a, const TraceTask* tasks, uint32_t n, uint8_t* area, hipStream_t s) {
+    if (n == 0) return;
+    const dim3 grid((n + 3) / 4), block(256);
+    switch (gapped_cells_per_lane(a.max_band)) {
+        case 2: hipLaunchKernelGGL(gapped_trace_kernel<2>, grid, block, 0, s, a, tasks, n, area); break;
+        case 4: hipLaunchKernelGGL(gapped_trace_kernel<4>, grid, block, 0, s, a, tasks, n, area); break;
+        case 8: hipLaunchKernelGGL(gapped_trace_kernel<8>, grid, block, 0, s, a, tasks, n, area); break;
+        case 17: hipLaunchKernelGGL(gapped_trace_kernel<17>, grid, block, 0, s, a, tasks, n, area); break;
+        default: hipLaunchKernelGGL(gapped_trace_kernel<33>, grid, block, 0, s, a, tasks, n, area); break;
+    }
+}
+
+void launch_gapped_walk(const GappedArgs& a, const TraceTask* tasks, uint32_t n, const uint8_t* area, uint32_t* ops, TraceOut* out,
+                        hipStream_t s) {
+    if (n == 0) return;
+    const dim3 grid((n + 3) / 4), block(256);
+    switch (gapped_cells_per_lane(a.max_band)) {
+        case 2: hipLaunchKernelGGL(gapped_walk_kernel<2>, grid, block, 0, s, a, tasks, n, area, ops, out); break;
+        case 4: hipLaunchKernelGGL(gapped_walk_kernel<4>, grid, block, 0, s, a, tasks, n, area, ops, out); break;
+        case 8: hipLaunchKernelGGL(gapped_walk_kernel<8>, grid, block, 0, s, a, tasks, n, area, ops, out); break;
+        case 17: hipLaunchKernelGGL(gapped_walk_kernel<17>, grid, block, 0, s, a, tasks, n, area, ops, out); break;
+        default: hipLaunchKernelGGL(gapped_walk_kernel<33>, grid, block, 0, s, a, tasks, n, area, ops, out); break;
+    }
 }
 
 void launch_gapped(const GappedArgs& a, hipStream_t s) {

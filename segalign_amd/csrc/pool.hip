@@ -89,6 +89,7 @@ void slot_destroy(Slot& s) {
     s.sort_temp.release("sort_temp"); s.unique_temp.release("unique_temp"); s.hits.release("hits"); s.recA.release("recA"); s.recB.release("recB");
     s.out16.release("out16");
     s.gapped.release("gapped");
+    s.gapped_trace.release("gapped trace");
     s.cand_list.release("candidate list");
     s.l2_list.release("second-level list");
     s.audit.release("audit list");

@@ -38,7 +38,7 @@ C_ABI_SYMBOLS = [
     "sa_seed_interval", "sa_seed_and_filter_chunks", "sa_max_chunks_per_call", "sa_get_chunks_per_call", "sa_extend_hits", "sa_order_hsps",
     "sa_get_lookup_mode", "sa_get_neighbourhood_entries",
     "sa_seed_calls", "sa_count_call_hits", "sa_count_chunk_hits", "sa_get_wga_chunk", "sa_release_arena", "sa_set_option", "sa_reset_option", "sa_get_option", "sa_option_count", "sa_option_name", "sa_get_audit",
-    "sa_gapped_extend", "sa_free_gapped",
+    "sa_gapped_extend", "sa_free_gapped", "sa_gapped_align", "sa_free_gapped_align",
 ]
 IVL_DTYPE = np.dtype([("query_start", "<u4"), ("len", "<u4")])  # struct Segment, repeat_masker_src/graph.h:32-35
 STRAND_PLUS, STRAND_MINUS, STRAND_BOTH = 1, 2, 3
@@ -59,6 +59,16 @@ class GappedParams(C.Structure):
 class GappedStats(C.Structure):
     _fields_ = [("anchors", C.c_uint64), ("cells", C.c_uint64), ("extent_capped", C.c_uint64), ("band_capped", C.c_uint64),
                 ("returned", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
+PATH_DTYPE = np.dtype([("op_offset", "<u8"), ("n_left", "<u4"), ("n_right", "<u4"), ("matches", "<u4"), ("mismatches", "<u4"),
+                       ("gap_opens", "<u4"), ("gap_bases", "<u4")])  # sa_gapped_path
+GAPPED_OP_M, GAPPED_OP_I, GAPPED_OP_D = 0, 1, 2
+
+
+class GappedAlignStats(C.Structure):
+    _fields_ = [("extend", GappedStats), ("trace_ms", C.c_double), ("walk_ms", C.c_double), ("trace_bytes", C.c_uint64),
+                ("trace_batches", C.c_uint64)]
 
 
 class CallStats(C.Structure):
@@ -157,6 +167,10 @@ def lib():
     L.sa_gapped_extend.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(GappedParams), C.c_int, C.POINTER(C.c_void_p),
                                    C.POINTER(GappedStats)]
     L.sa_free_gapped.argtypes = [C.c_void_p]
+    L.sa_gapped_align.restype = C.c_size_t
+    L.sa_gapped_align.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(GappedParams), C.c_int, C.POINTER(C.c_void_p),
+                                  C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(GappedAlignStats)]
+    L.sa_free_gapped_align.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -348,6 +362,33 @@ def GappedExtend(hsps, rev, buffer, gap_open=400, gap_extend=30, ydrop=9430, gap
     if out.value:
         lib().sa_free_gapped(out)
     return recs, {k: getattr(st, k) for k, _ in GappedStats._fields_}
+
+
+def GappedAlign(hsps, rev, buffer, gap_open=400, gap_extend=30, ydrop=9430, gappedthresh=3000, max_extent=0, max_band=0, raw=False):
+    """GappedExtend plus the alignment path of every record (sa_gapped_align; contract in include/segalign_amd.h).
+    -> (GAPPED_DTYPE records, PATH_DTYPE paths, uint32 ops, stats dict).  Record k's ops are
+    ops[paths[k].op_offset:][:n_left + n_right], the left side's runs first; decode them with cigar()."""
+    h = np.ascontiguousarray(hsps, dtype=SEG_DTYPE)
+    p = GappedParams(int(gap_open), int(gap_extend), int(ydrop), int(gappedthresh), int(max_extent), int(max_band))
+    out, paths, ops, n_ops = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
+    st = GappedAlignStats()
+    n = lib().sa_gapped_align(h.ctypes.data if h.size else None, h.size, int(bool(rev)), buffer, C.byref(p), int(bool(raw)),
+                              C.byref(out), C.byref(paths), C.byref(ops), C.byref(n_ops), C.byref(st))
+
+    def take(ptr, count, dtype):
+        if not count or not ptr.value:
+            return np.zeros(0, dtype=dtype)
+        return np.frombuffer((C.c_char * (count * dtype.itemsize)).from_address(ptr.value), dtype=dtype).copy()
+    recs, pth, o = take(out, n, GAPPED_DTYPE), take(paths, n, PATH_DTYPE), take(ops, n_ops.value, np.dtype("<u4"))
+    lib().sa_free_gapped_align(out, paths, ops)
+    stats = {k: getattr(st.extend, k) for k, _ in GappedStats._fields_}
+    stats.update({k: getattr(st, k) for k, _ in GappedAlignStats._fields_ if k != "extend"})
+    return recs, pth, o, stats
+
+
+def cigar(ops):
+    """Run-length ops (uint32 (length << 2) | op) as a CIGAR string: M aligned pair, I query base, D target base."""
+    return "".join("%d%s" % (int(x) >> 2, "MID"[int(x) & 3]) for x in ops)
 
 
 def SeedInterval(start, end, q_len, strands=STRAND_BOTH, buffer=0, threads=2):

@@ -39,6 +39,7 @@ struct Config {  // src/graph.h:32-76 with the defaults of src/main.cpp:61-124
     uint32_t step = 1;
     bool transition = true, noentropy = false, gapped = true, notrivial = false, debug = false, host_seeding = false;
     bool gpu_gapped = false;  // --gpu_gapped: a .gapped file next to every .segments file (sa_gapped_extend)
+    bool gpu_maf = false;     // --gpu_maf (with --gpu_gapped): a .maf file of the same alignments next to every .gapped file (sa_gapped_align)
     int gap_open = 400, gap_extend = 30;
     int xdrop = 910, hspthresh = 3000, ydrop = 9430, gappedthresh = -1;
     uint32_t wga_chunk = 250000, lastz_interval = 10000000, seq_block_size = 500000000;
@@ -235,7 +236,11 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
         if (cfg.gpu_gapped) {  // the gapped extension of the same HSPs on the device: [start, end) extents printed like the segments
             sa_gapped_params gp = {cfg.gap_open, cfg.gap_extend, cfg.ydrop, cfg.gappedthresh, 0, 0};
             sa_gapped_alignment* al = nullptr;
-            const size_t na = sa_gapped_extend(v.data(), v.size(), rev, buffer, &gp, 0, &al, nullptr);
+            sa_gapped_path* paths = nullptr;
+            uint32_t* ops = nullptr;
+            size_t n_ops = 0;
+            const size_t na = cfg.gpu_maf ? sa_gapped_align(v.data(), v.size(), rev, buffer, &gp, 0, &al, &paths, &ops, &n_ops, nullptr)
+                                          : sa_gapped_extend(v.data(), v.size(), rev, buffer, &gp, 0, &al, nullptr);
             std::string gname = base + ".gapped";
             FILE* g = fopen((cfg.outdir + "/" + gname).c_str(), "w");
             if (!g) die(7, "cant open file: %s", gname.c_str());
@@ -249,7 +254,39 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
             if (!rev) for (size_t i = 0; i < na; i++) emit_gapped(al[i]);
             else for (size_t i = na; i-- > 0;) emit_gapped(al[i]);  // reverse order on the minus strand, as the segments
             fclose(g);
-            sa_free_gapped(al);
+            if (cfg.gpu_maf) {  // LASTZ's maf- blocks (no header): 0-based starts within the record, minus-strand query in rc coordinates
+                std::string mname = base + ".maf";
+                FILE* mf = fopen((cfg.outdir + "/" + mname).c_str(), "w");
+                if (!mf) die(7, "cant open file: %s", mname.c_str());
+                const std::string& qbuf = rev ? Qrc : Q.buf;
+                const std::vector<uint32_t>& ql = rev ? rc_chr_len : Q.chr_len;
+                auto emit_maf = [&](size_t k) {
+                    const sa_gapped_alignment& a = al[k];
+                    const sa_gapped_path& p = paths[k];
+                    size_t r0 = a.ref_start + r_block_start, q0 = a.query_start + q_block_start;
+                    size_t ri = chr_of(R.chr_start, r0), qi = chr_of(qs, q0);
+                    std::string ta, qa;
+                    size_t i = r0, j = q0;
+                    for (size_t x = p.op_offset; x < p.op_offset + p.n_left + p.n_right; x++) {
+                        const size_t len = ops[x] >> 2, op = ops[x] & 3u;
+                        if (op == SA_GAPPED_OP_I) ta.append(len, '-');
+                        else { ta.append(R.buf, i, len); i += len; }
+                        if (op == SA_GAPPED_OP_D) qa.append(len, '-');
+                        else { qa.append(qbuf, j, len); j += len; }
+                    }
+                    fprintf(mf, "a score=%d\n", a.score);
+                    fprintf(mf, "s %s %zu %u + %u %s\n", R.chr_name[ri].c_str(), r0 - R.chr_start[ri], a.ref_end - a.ref_start, R.chr_len[ri],
+                            ta.c_str());
+                    fprintf(mf, "s %s %zu %u %c %u %s\n\n", qn[qi].c_str(), q0 - qs[qi], a.query_end - a.query_start, rev ? '-' : '+', ql[qi],
+                            qa.c_str());
+                };
+                if (!rev) for (size_t k = 0; k < na; k++) emit_maf(k);
+                else for (size_t k = na; k-- > 0;) emit_maf(k);  // the .gapped file's order
+                fclose(mf);
+                sa_free_gapped_align(al, paths, ops);
+            } else {
+                sa_free_gapped(al);
+            }
         }
         if (cfg.gapped) {  // :96-113 / :151-168
             std::string cmd = "lastz " + cfg.data_folder + "ref.2bit[nameparse=darkspace][multiple][subset=ref_block" +
@@ -275,7 +312,8 @@ static void usage() {
             "  --ambiguous=x|n|iupac[,reward,penalty] --scoring=FILE\n"
             "  --wga_chunk=N --lastz_interval=N --seq_block_size=N --num_gpu=N --num_threads=N --outdir=DIR\n"
             "  --host-seeding (build seed vectors on the host like src/seeder.cpp) --debug\n"
-            "  --gpu_gapped [--gap=O,E] (gapped y-drop extension on the GPU: a .gapped file next to each .segments file)\n");
+            "  --gpu_gapped [--gap=O,E] (gapped y-drop extension on the GPU: a .gapped file next to each .segments file)\n"
+            "  --gpu_maf (with --gpu_gapped: the alignments of each .gapped file as a .maf file in LASTZ's maf- layout)\n");
 }
 
 int main(int argc, char** argv) {
@@ -309,6 +347,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(a, "--host-seeding")) cfg.host_seeding = true;
         else if (!strcmp(a, "--debug")) cfg.debug = true;
         else if (!strcmp(a, "--gpu_gapped")) cfg.gpu_gapped = true;
+        else if (!strcmp(a, "--gpu_maf")) cfg.gpu_maf = true;
         else if (opt(a, "--gap", v)) {
             if (sscanf(v.c_str(), "%d,%d", &cfg.gap_open, &cfg.gap_extend) != 2) { fprintf(stderr, "bad --gap=%s\n", v.c_str()); return 1; }
         }

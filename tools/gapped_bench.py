@@ -1,8 +1,9 @@
 """Gapped extension throughput: one forty-chunk call (10 Mbp of one query strand) through sa_seed_calls, then its HSPs through
 sa_gapped_extend with the default parameters.  Prints one JSON line per workload: anchors, live cells, cells per anchor, flag
-counts, kernel ms and giga-cells per second (cells / kernel time).
+counts, kernel ms and giga-cells per second (cells / kernel time).  With --align the same HSPs also go through sa_gapped_align:
+the line then adds its extension, trace-sweep and walk ms, the trace bytes and batches, and the ops returned.
 
-  python tools/gapped_bench.py [--workloads standin,lumpy] [--repeat 3]
+  python tools/gapped_bench.py [--workloads standin,lumpy] [--repeat 3] [--align]
 """
 import argparse
 import json
@@ -40,7 +41,7 @@ def workload(name):
     raise SystemExit("unknown workload %s" % name)
 
 
-def run(name, repeat):
+def run(name, repeat, align=False):
     t, q = workload(name)
     E.InitializeInterface(1)
     E.GenerateShapePos(SHAPE)
@@ -59,21 +60,39 @@ def run(name, repeat):
         if best is None or st["kernel_ms"] < best[1]["kernel_ms"]:
             best = (recs, st, wall)
     recs, st, wall = best
+    extra = {}
+    if align:
+        best_a = None
+        for _ in range(repeat):
+            t0 = time.perf_counter()
+            arecs, paths, ops, ast = E.GappedAlign(hsps, False, 0)
+            awall = (time.perf_counter() - t0) * 1e3
+            total = ast["kernel_ms"] + ast["trace_ms"] + ast["walk_ms"]
+            if best_a is None or total < best_a[0]:
+                best_a = (total, arecs, ops, ast, awall)
+        total, arecs, ops, ast, awall = best_a
+        if not np.array_equal(arecs, recs):
+            raise SystemExit("sa_gapped_align returned other records than sa_gapped_extend")
+        extra = {"align_extend_ms": round(ast["kernel_ms"], 3), "align_trace_ms": round(ast["trace_ms"], 3),
+                 "align_walk_ms": round(ast["walk_ms"], 3), "align_kernel_ms": round(total, 3), "align_call_ms": round(awall, 3),
+                 "align_over_extend": round(total / st["kernel_ms"], 3) if st["kernel_ms"] > 0 else None,
+                 "trace_bytes": int(ast["trace_bytes"]), "trace_batches": int(ast["trace_batches"]), "ops": int(ops.size)}
     E.ShutdownProcessor()
     return {"workload": name, "call": list(call), "anchors": int(st["anchors"]), "alignments": int(st["returned"]),
             "cells": int(st["cells"]), "cells_per_anchor": st["cells"] / max(st["anchors"], 1),
             "extent_capped": int(st["extent_capped"]), "band_capped": int(st["band_capped"]),
             "kernel_ms": round(st["kernel_ms"], 3), "call_ms": round(wall, 3),
-            "gcells_per_s": round(st["cells"] / (st["kernel_ms"] * 1e-3) / 1e9, 3) if st["kernel_ms"] > 0 else None}
+            "gcells_per_s": round(st["cells"] / (st["kernel_ms"] * 1e-3) / 1e9, 3) if st["kernel_ms"] > 0 else None, **extra}
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="standin,lumpy")
     ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--align", action="store_true", help="also time sa_gapped_align on the same HSPs")
     a = ap.parse_args()
     for name in a.workloads.split(","):
-        print(json.dumps(run(name, a.repeat)), flush=True)
+        print(json.dumps(run(name, a.repeat, a.align)), flush=True)
 
 
 if __name__ == "__main__":
