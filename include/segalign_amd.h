@@ -234,6 +234,11 @@ int sa_max_hits_for_mem(uint64_t total_global_mem);
  *                     1 hipMemcpyAsync from the pageable vector (the runtime stages it), 2 hipHostRegister the vector + DMA
  *   gapped_trace_mb   MiB of trace area one sa_gapped_align batch packs its traced sides into (default 1024; a side that needs more
  *                     runs in a batch of its own and grows the slot's buffer to fit).  Each slot keeps its buffer until shutdown
+ *   gapped_greedy_batch  anchors per priority batch of sa_gapped_align_greedy (default 1024; 1 .. 1 << 20).  Its records and its
+ *                     covered / below_thresh counts do not depend on it; only skipped and the work done do
+ *   gapped_greedy_edges  in-edges one resolve pass of sa_gapped_align_greedy holds (default 1 << 26, 4 bytes each; 1 .. 1 << 32).  Anchors
+ *                     that cover each other pairwise give quadratically many; a batch with more is resolved in several passes, with the
+ *                     same result.  Option debug prints the edge count of every call to stderr
  * Launch geometry (defaults are the measured optima, tools/sweep_*.sh)
  *   fin_batch, bufs_per_wave, long_cap, long_blocks, max_waves, packed_waves, l2_blocks, ctx_waves, ctx_threads,
  *   chain_sort_threads, chain_sort_blocks, chain_group_max (candidates a chain workgroup sorts in LDS at a time), chain_bucket_target
@@ -365,8 +370,9 @@ size_t sa_order_hsps(const sa_segment_pair* in, size_t n, int rm, int path, sa_s
  * Selection (raw = 0): (1) keep score >= gappedthresh; (2) of records with identical (ref_start, ref_end, query_start, query_end)
  *   keep the highest score, on a tie the lowest hsp_index; (3) order by (query_start, ref_start, query_end, ref_end, -score,
  *   hsp_index).  raw != 0: one record per input HSP in input order, no threshold, no de-duplication.
- * Not done: LASTZ's skipping of anchors inside earlier alignments (redundant anchors are extended and removed by rule (2)),
- *   bit-identity with LASTZ.  The alignment path of each record (traceback) is sa_gapped_align's, below. */
+ * Not done here: LASTZ's skipping of anchors inside earlier alignments (redundant anchors are extended and removed by rule (2); the
+ *   skipping is sa_gapped_align_greedy's, below), bit-identity with LASTZ.  The alignment path of each record (traceback) is
+ *   sa_gapped_align's, below. */
 #define SA_GAPPED_EXTENT_CAP 1u /* a side reached max_extent bases */
 #define SA_GAPPED_BAND_CAP 2u   /* a side ended at the band cap */
 
@@ -473,6 +479,43 @@ _Static_assert(sizeof(sa_gapped_align_stats) == 80, "sa_gapped_align_stats is 80
 size_t sa_gapped_align(const sa_segment_pair* hsps, size_t n, int rev, uint32_t buffer, const sa_gapped_params* p, int raw,
                        sa_gapped_alignment** out, sa_gapped_path** paths, uint32_t** ops, size_t* n_ops, sa_gapped_align_stats* stats);
 void sa_free_gapped_align(sa_gapped_alignment* out, sa_gapped_path* paths, uint32_t* ops);
+
+/* ---- skipping anchors that lie on earlier alignments (additive) ----------------------------------------
+ *
+ * sa_gapped_align_greedy extends anchors best first and skips an anchor that lies on an alignment it has already accepted, in the spirit
+ * of LASTZ (not claimed to equal it).  The definition is sequential; the implementation resolves it exactly in parallel batches.
+ *   Priority pi: the HSPs ordered by (score descending, input index ascending).  The anchor (a_r, a_q) is sa_gapped_extend's.
+ *   Cover set of an alignment: the (t, q) of its M pairs, found by walking its ops from (ref_start, query_start) in strand `rev`
+ *     coordinates, plus its own anchor point (so that duplicate HSPs give one record even when a path starts with a gap at its anchor).
+ *   Sequential rule: A = {}; for h in pi order: if h's anchor is in the cover set of a member of A, h is covered and gives no record;
+ *     otherwise h's record and path are computed -- bit-identical to sa_gapped_align raw mode for that HSP -- and h joins A if its score
+ *     is >= gappedthresh, else it is below threshold and covers nothing.
+ *   Output: the records of A in selection rule (3)'s order with their paths and ops laid out as sa_gapped_align lays them out.  Rule (2)
+ *     does not apply: every input HSP is exactly one of returned, covered (by a returned record of higher priority) or below threshold.
+ *   Scope: one call, which is one strand of one query buffer.  Covering does not reach across calls.
+ * Parameters, defaults, limits, thread safety and the release function are sa_gapped_align's.  Option gapped_greedy_batch sets the
+ * anchors per priority batch; the records, covered and below_thresh do not depend on it, skipped and the work done do. */
+typedef struct sa_gapped_greedy_stats {
+    sa_gapped_align_stats align; /* as sa_gapped_align reports them, over the anchors actually extended and traced */
+    uint64_t covered;            /* HSPs whose anchor lies on an accepted alignment (batch-independent) */
+    uint64_t below_thresh;       /* HSPs not covered whose score < gappedthresh (batch-independent) */
+    uint64_t skipped;            /* covered HSPs found covered before extension (never extended) */
+    uint64_t priority_batches;   /* batches of option gapped_greedy_batch */
+    uint64_t cover_segments;     /* entries of the cover index at the end of the call: the accepted paths' M runs plus one
+                                    unit segment per accepted anchor point */
+    double cover_ms;             /* device time of the cover-index, query, edge and resolve kernels */
+} sa_gapped_greedy_stats;
+#ifdef __cplusplus
+static_assert(sizeof(sa_gapped_greedy_stats) == 128, "sa_gapped_greedy_stats is 128 bytes");
+#else
+_Static_assert(sizeof(sa_gapped_greedy_stats) == 128, "sa_gapped_greedy_stats is 128 bytes");
+#endif
+
+/* Returns the number of records; *out, *paths, *ops and *n_ops as sa_gapped_align returns them (release with sa_free_gapped_align).
+ * stats: nullable. */
+size_t sa_gapped_align_greedy(const sa_segment_pair* hsps, size_t n, int rev, uint32_t buffer, const sa_gapped_params* p,
+                              sa_gapped_alignment** out, sa_gapped_path** paths, uint32_t** ops, size_t* n_ops,
+                              sa_gapped_greedy_stats* stats);
 
 const char* sa_version(void);
 

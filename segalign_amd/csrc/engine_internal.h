@@ -241,6 +241,8 @@ int prof_id(const char* name);
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int MAX_SLOTS_PER_DEVICE = 8;
 extern int64_t g_gapped_trace_mb;  // option gapped_trace_mb: MiB of trace area per sa_gapped_align batch
+extern int64_t g_gapped_greedy_batch;  // option gapped_greedy_batch: anchors per priority batch of sa_gapped_align_greedy
+extern int64_t g_gapped_greedy_edges;  // option gapped_greedy_edges: in-edges one resolve pass of sa_gapped_align_greedy holds
 extern uint32_t SPEC_RECS;        // records of the speculative output copy (256 KB); option spec_recs (tests)
 extern uint32_t g_dedup_seg_max;  // option dedup_seg_max: records per segment the LDS chain accepts (0 = its LDS capacity; tests)
 constexpr int SA_MAX_CHUNKS = 256;  // chunks one multi-chunk call may carry: 2 reference iterations each = MAX_SEGS segments
@@ -337,6 +339,11 @@ struct Slot {
     WorkRegion work;                  // this slot's share of the device's work arena
     DevBuf<uint8_t> gapped;           // sa_gapped_extend: a batch's HSPs and its per-side results (api_gapped.hip)
     DevBuf<uint8_t> gapped_trace;     // sa_gapped_align: a batch's side tasks, walk results, op areas and trace areas (api_gapped.hip)
+    // sa_gapped_align_greedy (api_gapped.hip, cover.hip): the cover index (keys and running maxima, double-buffered for the merge), a
+    // priority batch's segments, its other per-batch arrays, its edges and rocPRIM's temporary storage
+    DevBuf<uint64_t> cover_key[2], cover_run[2];
+    DevBuf<uint8_t> cover_segs, cover_work, cover_temp;
+    DevBuf<uint32_t> cover_edges;
 };
 
 // ------------------------------------------------------------------------------------------------------------------

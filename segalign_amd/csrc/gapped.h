@@ -55,4 +55,53 @@ void launch_gapped_trace(const GappedArgs& a, const TraceTask* tasks, uint32_t n
 void launch_gapped_walk(const GappedArgs& a, const TraceTask* tasks, uint32_t n, const uint8_t* area, uint32_t* ops, TraceOut* out,
                         hipStream_t s);
 
+// ---- cover index of sa_gapped_align_greedy (cover.hip) ----
+// A point (t, q) of strand coordinates lies on diagonal diag = t - q + query_len; its key is diag << 32 | t.  An M run of a path is the
+// segment [t_begin, t_end) of one diagonal, keyed by its first point.
+constexpr uint64_t COVER_NONE = ~0ull;  // key of a segment slot that holds no M run (sorts last)
+constexpr uint32_t COVER_RESOLVE_MAX = 1u << 20;  // survivors one resolve launch takes (accepted bits in dynamic LDS, 128 KB at most)
+
+struct CoverSeg {
+    uint64_t key;    // diag << 32 | t_begin, or COVER_NONE
+    uint32_t t_end;  // one past the segment's last target base
+    uint32_t owner;  // the survivor (rank in its priority batch) whose path holds the segment
+};
+
+struct CoverEmit {    // one traced side: where its segments go
+    uint32_t seg_off;  // first of its n_runs segment slots
+    uint32_t owner;
+};
+
+// One wave per traced side of a trace batch: the side's runs (d_ops, walk order) become n_runs segment slots, M runs keyed, the rest
+// COVER_NONE.  Runs before the walk's buffers are reused by the next trace batch.
+void launch_cover_emit(const TraceTask* tasks, const TraceOut* out, const uint32_t* ops, const CoverEmit* emit, uint32_t n,
+                       uint32_t query_len, CoverSeg* segs, hipStream_t s);
+// covered[k] = 1 when point key keys[k] lies on a segment of the index (key[], run[]: sorted keys and the running maximum of t_end
+// within each diagonal, packed diag << 32 | max).
+void launch_cover_query(const uint64_t* key, const uint64_t* run, uint32_t n_index, const uint64_t* keys, uint32_t n, uint8_t* covered,
+                        hipStream_t s);
+// Edges (owner a -> survivor h) of one resolve pass over the survivor ranks [lo, hi): every segment of a survivor a >= lo with
+// eligible[a] != 0 and every survivor anchor h on it with a < h < hi.  akey / arank: the survivors' anchor keys sorted, with their ranks.
+// Indices are local to the pass (h - lo, a - lo).  count != 0: deg[h - lo] += 1; otherwise src[cursor[h - lo]++] = a - lo.
+void launch_cover_edges(const CoverSeg* segs, uint32_t n_segs, const uint64_t* akey, const uint32_t* arank, uint32_t n_anchors,
+                        const uint8_t* eligible, uint32_t lo, uint32_t hi, uint32_t* deg, uint64_t* cursor, uint32_t* src, int count,
+                        hipStream_t s);
+// One wave sweeps the n survivors of a pass in rank order: state[h] = 1 accepted (eligible, no in-edge from an accepted survivor), 2
+// covered (an in-edge from an accepted survivor), 0 below the threshold.  row: CSR offsets [n + 1] of the in-edges (local indices).
+void launch_cover_resolve(const uint8_t* eligible, const uint64_t* row, const uint32_t* src, uint32_t n, uint8_t* state, hipStream_t s);
+// The segments of accepted owners (state 1) with ranks in [lo, hi) appended to key[] / dt[] (dt = diag << 32 | t_end) at atomic
+// positions; *count: how many.
+void launch_cover_select(const CoverSeg* segs, uint32_t n_segs, const uint8_t* state, uint32_t lo, uint32_t hi, uint64_t* key, uint64_t* dt,
+                         uint32_t* count, hipStream_t s);
+// Merges (ka, va)[na] and (kb, vb)[nb], both sorted by key, into (ko, vo)[na + nb]; equal keys keep a's entries first.
+void launch_cover_merge(const uint64_t* ka, const uint64_t* va, uint32_t na, const uint64_t* kb, const uint64_t* vb, uint32_t nb,
+                        uint64_t* ko, uint64_t* vo, hipStream_t s);
+// rocPRIM steps.  temp == nullptr: *bytes = temp storage needed.
+void cover_sort_pairs(void* temp, size_t* bytes, const uint64_t* kin, uint64_t* kout, const uint64_t* vin, uint64_t* vout, uint32_t n,
+                      hipStream_t s);
+void cover_sort_anchors(void* temp, size_t* bytes, const uint64_t* kin, uint64_t* kout, const uint32_t* vin, uint32_t* vout, uint32_t n,
+                        hipStream_t s);
+void cover_scan_offsets(void* temp, size_t* bytes, const uint32_t* deg, uint64_t* row, uint32_t n, hipStream_t s);  // row[n + 1], 64-bit
+void cover_scan_runmax(void* temp, size_t* bytes, const uint64_t* dt, uint64_t* run, uint32_t n, hipStream_t s);
+
 }  // namespace sa

@@ -90,6 +90,14 @@ void slot_destroy(Slot& s) {
     s.out16.release("out16");
     s.gapped.release("gapped");
     s.gapped_trace.release("gapped trace");
+    for (int i = 0; i < 2; i++) {
+        s.cover_key[i].release("cover index");
+        s.cover_run[i].release("cover index");
+    }
+    s.cover_segs.release("cover segments");
+    s.cover_work.release("cover work");
+    s.cover_temp.release("cover temp");
+    s.cover_edges.release("cover edges");
     s.cand_list.release("candidate list");
     s.l2_list.release("second-level list");
     s.audit.release("audit list");

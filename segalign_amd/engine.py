@@ -38,7 +38,7 @@ C_ABI_SYMBOLS = [
     "sa_seed_interval", "sa_seed_and_filter_chunks", "sa_max_chunks_per_call", "sa_get_chunks_per_call", "sa_extend_hits", "sa_order_hsps",
     "sa_get_lookup_mode", "sa_get_neighbourhood_entries",
     "sa_seed_calls", "sa_count_call_hits", "sa_count_chunk_hits", "sa_get_wga_chunk", "sa_release_arena", "sa_set_option", "sa_reset_option", "sa_get_option", "sa_option_count", "sa_option_name", "sa_get_audit",
-    "sa_gapped_extend", "sa_free_gapped", "sa_gapped_align", "sa_free_gapped_align",
+    "sa_gapped_extend", "sa_free_gapped", "sa_gapped_align", "sa_free_gapped_align", "sa_gapped_align_greedy",
 ]
 IVL_DTYPE = np.dtype([("query_start", "<u4"), ("len", "<u4")])  # struct Segment, repeat_masker_src/graph.h:32-35
 STRAND_PLUS, STRAND_MINUS, STRAND_BOTH = 1, 2, 3
@@ -69,6 +69,11 @@ GAPPED_OP_M, GAPPED_OP_I, GAPPED_OP_D = 0, 1, 2
 class GappedAlignStats(C.Structure):
     _fields_ = [("extend", GappedStats), ("trace_ms", C.c_double), ("walk_ms", C.c_double), ("trace_bytes", C.c_uint64),
                 ("trace_batches", C.c_uint64)]
+
+
+class GappedGreedyStats(C.Structure):
+    _fields_ = [("align", GappedAlignStats), ("covered", C.c_uint64), ("below_thresh", C.c_uint64), ("skipped", C.c_uint64),
+                ("priority_batches", C.c_uint64), ("cover_segments", C.c_uint64), ("cover_ms", C.c_double)]
 
 
 class CallStats(C.Structure):
@@ -171,6 +176,9 @@ def lib():
     L.sa_gapped_align.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(GappedParams), C.c_int, C.POINTER(C.c_void_p),
                                   C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(GappedAlignStats)]
     L.sa_free_gapped_align.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sa_gapped_align_greedy.restype = C.c_size_t
+    L.sa_gapped_align_greedy.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(GappedParams), C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(GappedGreedyStats)]
     _lib = L
     return L
 
@@ -383,6 +391,29 @@ def GappedAlign(hsps, rev, buffer, gap_open=400, gap_extend=30, ydrop=9430, gapp
     lib().sa_free_gapped_align(out, paths, ops)
     stats = {k: getattr(st.extend, k) for k, _ in GappedStats._fields_}
     stats.update({k: getattr(st, k) for k, _ in GappedAlignStats._fields_ if k != "extend"})
+    return recs, pth, o, stats
+
+
+def GappedAlignGreedy(hsps, rev, buffer, gap_open=400, gap_extend=30, ydrop=9430, gappedthresh=3000, max_extent=0, max_band=0):
+    """GappedAlign's records and paths, but anchors are extended best first and one that lies on an alignment accepted before it is
+    skipped (sa_gapped_align_greedy; contract in include/segalign_amd.h).  -> (GAPPED_DTYPE records, PATH_DTYPE paths,
+    uint32 ops, stats dict): GappedAlign's stats plus covered, below_thresh, skipped, priority_batches, cover_segments, cover_ms."""
+    h = np.ascontiguousarray(hsps, dtype=SEG_DTYPE)
+    p = GappedParams(int(gap_open), int(gap_extend), int(ydrop), int(gappedthresh), int(max_extent), int(max_band))
+    out, paths, ops, n_ops = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
+    st = GappedGreedyStats()
+    n = lib().sa_gapped_align_greedy(h.ctypes.data if h.size else None, h.size, int(bool(rev)), buffer, C.byref(p), C.byref(out),
+                                     C.byref(paths), C.byref(ops), C.byref(n_ops), C.byref(st))
+
+    def take(ptr, count, dtype):
+        if not count or not ptr.value:
+            return np.zeros(0, dtype=dtype)
+        return np.frombuffer((C.c_char * (count * dtype.itemsize)).from_address(ptr.value), dtype=dtype).copy()
+    recs, pth, o = take(out, n, GAPPED_DTYPE), take(paths, n, PATH_DTYPE), take(ops, n_ops.value, np.dtype("<u4"))
+    lib().sa_free_gapped_align(out, paths, ops)
+    stats = {k: getattr(st.align.extend, k) for k, _ in GappedStats._fields_}
+    stats.update({k: getattr(st.align, k) for k, _ in GappedAlignStats._fields_ if k != "extend"})
+    stats.update({k: getattr(st, k) for k, _ in GappedGreedyStats._fields_ if k != "align"})
     return recs, pth, o, stats
 
 

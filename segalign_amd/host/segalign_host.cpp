@@ -40,6 +40,7 @@ struct Config {  // src/graph.h:32-76 with the defaults of src/main.cpp:61-124
     bool transition = true, noentropy = false, gapped = true, notrivial = false, debug = false, host_seeding = false;
     bool gpu_gapped = false;  // --gpu_gapped: a .gapped file next to every .segments file (sa_gapped_extend)
     bool gpu_maf = false;     // --gpu_maf (with --gpu_gapped): a .maf file of the same alignments next to every .gapped file (sa_gapped_align)
+    bool gpu_skip_covered = false;  // --gpu_skip_covered (with --gpu_gapped): the files hold sa_gapped_align_greedy's alignments
     int gap_open = 400, gap_extend = 30;
     int xdrop = 910, hspthresh = 3000, ydrop = 9430, gappedthresh = -1;
     uint32_t wga_chunk = 250000, lastz_interval = 10000000, seq_block_size = 500000000;
@@ -239,8 +240,10 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
             sa_gapped_path* paths = nullptr;
             uint32_t* ops = nullptr;
             size_t n_ops = 0;
-            const size_t na = cfg.gpu_maf ? sa_gapped_align(v.data(), v.size(), rev, buffer, &gp, 0, &al, &paths, &ops, &n_ops, nullptr)
-                                          : sa_gapped_extend(v.data(), v.size(), rev, buffer, &gp, 0, &al, nullptr);
+            const bool with_paths = cfg.gpu_maf || cfg.gpu_skip_covered;
+            const size_t na = cfg.gpu_skip_covered ? sa_gapped_align_greedy(v.data(), v.size(), rev, buffer, &gp, &al, &paths, &ops, &n_ops, nullptr)
+                              : cfg.gpu_maf        ? sa_gapped_align(v.data(), v.size(), rev, buffer, &gp, 0, &al, &paths, &ops, &n_ops, nullptr)
+                                                   : sa_gapped_extend(v.data(), v.size(), rev, buffer, &gp, 0, &al, nullptr);
             std::string gname = base + ".gapped";
             FILE* g = fopen((cfg.outdir + "/" + gname).c_str(), "w");
             if (!g) die(7, "cant open file: %s", gname.c_str());
@@ -283,10 +286,9 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
                 if (!rev) for (size_t k = 0; k < na; k++) emit_maf(k);
                 else for (size_t k = na; k-- > 0;) emit_maf(k);  // the .gapped file's order
                 fclose(mf);
-                sa_free_gapped_align(al, paths, ops);
-            } else {
-                sa_free_gapped(al);
             }
+            if (with_paths) sa_free_gapped_align(al, paths, ops);
+            else sa_free_gapped(al);
         }
         if (cfg.gapped) {  // :96-113 / :151-168
             std::string cmd = "lastz " + cfg.data_folder + "ref.2bit[nameparse=darkspace][multiple][subset=ref_block" +
@@ -313,7 +315,8 @@ static void usage() {
             "  --wga_chunk=N --lastz_interval=N --seq_block_size=N --num_gpu=N --num_threads=N --outdir=DIR\n"
             "  --host-seeding (build seed vectors on the host like src/seeder.cpp) --debug\n"
             "  --gpu_gapped [--gap=O,E] (gapped y-drop extension on the GPU: a .gapped file next to each .segments file)\n"
-            "  --gpu_maf (with --gpu_gapped: the alignments of each .gapped file as a .maf file in LASTZ's maf- layout)\n");
+            "  --gpu_maf (with --gpu_gapped: the alignments of each .gapped file as a .maf file in LASTZ's maf- layout)\n"
+            "  --gpu_skip_covered (with --gpu_gapped: extend anchors best first and skip those on earlier alignments)\n");
 }
 
 int main(int argc, char** argv) {
@@ -348,6 +351,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(a, "--debug")) cfg.debug = true;
         else if (!strcmp(a, "--gpu_gapped")) cfg.gpu_gapped = true;
         else if (!strcmp(a, "--gpu_maf")) cfg.gpu_maf = true;
+        else if (!strcmp(a, "--gpu_skip_covered")) cfg.gpu_skip_covered = true;
         else if (opt(a, "--gap", v)) {
             if (sscanf(v.c_str(), "%d,%d", &cfg.gap_open, &cfg.gap_extend) != 2) { fprintf(stderr, "bad --gap=%s\n", v.c_str()); return 1; }
         }

@@ -1,14 +1,19 @@
 """Gapped extension throughput: one forty-chunk call (10 Mbp of one query strand) through sa_seed_calls, then its HSPs through
 sa_gapped_extend with the default parameters.  Prints one JSON line per workload: anchors, live cells, cells per anchor, flag
 counts, kernel ms and giga-cells per second (cells / kernel time).  With --align the same HSPs also go through sa_gapped_align:
-the line then adds its extension, trace-sweep and walk ms, the trace bytes and batches, and the ops returned.
+the line then adds its extension, trace-sweep and walk ms, the trace bytes and batches, and the ops returned.  With --greedy the same
+HSPs go through sa_gapped_align in selection mode and through sa_gapped_align_greedy: the line then adds, for both, the anchors
+extended, returned, covered, skipped and below threshold and the extension / trace / walk / cover ms.
 
-  python tools/gapped_bench.py [--workloads standin,lumpy] [--repeat 3] [--align]
+  python tools/gapped_bench.py [--workloads standin,lumpy] [--repeat 3] [--align] [--greedy] [--batches 1024,2048,...]
 """
 import argparse
+import functools
 import json
 import os
+import re
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,6 +38,7 @@ SUB = np.array([
     [-9100] * 8], dtype=np.int32).reshape(64)
 
 
+@functools.lru_cache(maxsize=None)
 def workload(name):
     if name == "standin":  # the 100 Mbp stand-in of bench.py / BASELINE configs[1]
         return synth.make_pair(100_000_000, 3, 4, sub_rate=0.08, mask_frac=0.2, records=7, invert_frac=0.3, invert_block=100_000)
@@ -41,8 +47,69 @@ def workload(name):
     raise SystemExit("unknown workload %s" % name)
 
 
-def run(name, repeat, align=False):
+def with_stderr(f):
+    """f() with file descriptor 2 captured: -> (result, what the library wrote to stderr)."""
+    sys.stderr.flush()
+    saved = os.dup(2)
+    with tempfile.TemporaryFile() as tmp:
+        os.dup2(tmp.fileno(), 2)
+        try:
+            r = f()
+        finally:
+            os.dup2(saved, 2)
+            os.close(saved)
+        tmp.seek(0)
+        return r, tmp.read().decode(errors="replace")
+
+
+def greedy_edges(text):
+    """(edges, largest pass, resolve passes) from the line option debug makes sa_gapped_align_greedy print."""
+    m = re.search(r"GappedAlignGreedy: \d+ HSPs, \d+ priority batches, (\d+) resolve passes, (\d+) edges \(at most (\d+)", text)
+    return (int(m.group(2)), int(m.group(3)), int(m.group(1))) if m else (None, None, None)
+
+
+def greedy_fields(hsps, repeat, with_sel=True):
+    """sa_gapped_align selection mode and sa_gapped_align_greedy on the same HSPs, the run with the least device time of each."""
+    def best_of(f):
+        best = None
+        for _ in range(repeat):
+            t0 = time.perf_counter()
+            r = f()
+            wall = (time.perf_counter() - t0) * 1e3
+            st = r[3]
+            total = st["kernel_ms"] + st["trace_ms"] + st["walk_ms"] + st.get("cover_ms", 0.0)
+            if best is None or total < best[0]:
+                best = (total, r, wall)
+        return best
+    g_total, (grecs, _, gops, gst), g_wall = best_of(lambda: E.GappedAlignGreedy(hsps, False, 0))
+    _, err = with_stderr(lambda: E.GappedAlignGreedy(hsps, False, 0))  # option debug is on: the call prints its edge count
+    n_edges, max_edges, passes = greedy_edges(err)
+    n = int(hsps.size)
+    sel = {}
+    s_total = None
+    if with_sel:
+        s_total, (srecs, _, _, sst), s_wall = best_of(lambda: E.GappedAlign(hsps, False, 0))
+        below = int(np.count_nonzero(E.GappedExtend(hsps, False, 0, raw=True)[0]["score"] < 3000))
+        sel = {"sel_anchors": n, "sel_extended": int(sst["anchors"]), "sel_returned": int(srecs.size), "sel_below_thresh": below,
+               "sel_extend_ms": round(sst["kernel_ms"], 3), "sel_trace_ms": round(sst["trace_ms"], 3), "sel_walk_ms": round(sst["walk_ms"], 3),
+               "sel_kernel_ms": round(s_total, 3), "sel_call_ms": round(s_wall, 3), "sel_trace_bytes": int(sst["trace_bytes"]),
+               "sel_trace_batches": int(sst["trace_batches"])}
+    return {**sel, "greedy_anchors": n, "greedy_extended": int(gst["anchors"]), "greedy_returned": int(grecs.size),
+            "greedy_covered": int(gst["covered"]), "greedy_skipped": int(gst["skipped"]), "greedy_below_thresh": int(gst["below_thresh"]),
+            "greedy_extend_ms": round(gst["kernel_ms"], 3), "greedy_trace_ms": round(gst["trace_ms"], 3),
+            "greedy_walk_ms": round(gst["walk_ms"], 3), "greedy_trace_bytes": int(gst["trace_bytes"]),
+            "greedy_trace_batches": int(gst["trace_batches"]), "greedy_traced_not_returned": int(gst["anchors"]) - int(grecs.size),
+            "edges": n_edges, "edges_max_pass": max_edges, "resolve_passes": passes, "greedy_cover_ms": round(gst["cover_ms"], 3), "greedy_kernel_ms": round(g_total, 3),
+            "greedy_call_ms": round(g_wall, 3), "greedy_over_sel": round(g_total / s_total, 3) if s_total else None,
+            "cover_share": round(gst["cover_ms"] / g_total, 4) if g_total > 0 else None, "priority_batches": int(gst["priority_batches"]),
+            "greedy_batch": int(E.get_option("gapped_greedy_batch")), "cover_segments": int(gst["cover_segments"]),
+            "trace_mb": int(E.get_option("gapped_trace_mb")), "greedy_ops": int(gops.size)}
+
+
+def run(name, repeat, align=False, greedy=False, with_sel=True):
     t, q = workload(name)
+    if greedy:
+        E.set_option("debug", 1)  # sa_gapped_align_greedy then prints its edge count
     E.InitializeInterface(1)
     E.GenerateShapePos(SHAPE)
     E.InitializeProcessor(True, 250_000, 19, SUB, 910, 3000, False)
@@ -77,7 +144,11 @@ def run(name, repeat, align=False):
                  "align_walk_ms": round(ast["walk_ms"], 3), "align_kernel_ms": round(total, 3), "align_call_ms": round(awall, 3),
                  "align_over_extend": round(total / st["kernel_ms"], 3) if st["kernel_ms"] > 0 else None,
                  "trace_bytes": int(ast["trace_bytes"]), "trace_batches": int(ast["trace_batches"]), "ops": int(ops.size)}
+    if greedy:
+        extra.update(greedy_fields(hsps, repeat, with_sel))
     E.ShutdownProcessor()
+    if greedy:
+        E.reset_option("debug")
     return {"workload": name, "call": list(call), "anchors": int(st["anchors"]), "alignments": int(st["returned"]),
             "cells": int(st["cells"]), "cells_per_anchor": st["cells"] / max(st["anchors"], 1),
             "extent_capped": int(st["extent_capped"]), "band_capped": int(st["band_capped"]),
@@ -90,9 +161,17 @@ def main():
     ap.add_argument("--workloads", default="standin,lumpy")
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--align", action="store_true", help="also time sa_gapped_align on the same HSPs")
+    ap.add_argument("--greedy", action="store_true", help="also time sa_gapped_align (selection mode) and sa_gapped_align_greedy")
+    ap.add_argument("--batches", default="", help="with --greedy: one line per gapped_greedy_batch value, greedy only (a sweep)")
     a = ap.parse_args()
     for name in a.workloads.split(","):
-        print(json.dumps(run(name, a.repeat, a.align)), flush=True)
+        if not a.batches:
+            print(json.dumps(run(name, a.repeat, a.align, a.greedy)), flush=True)
+            continue
+        for b in a.batches.split(","):
+            E.set_option("gapped_greedy_batch", int(b))
+            print(json.dumps(run(name, a.repeat, a.align, True, with_sel=False)), flush=True)
+        E.reset_option("gapped_greedy_batch")
 
 
 if __name__ == "__main__":
