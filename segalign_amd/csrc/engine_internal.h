@@ -11,7 +11,7 @@
 //   api_setup.hip      InitializeInterface / InitializeProcessor / Shutdown, target + query upload, GenerateSeedPosTable
 //   api_calls.hip      SeedAndFilter and its additive forms (range, chunks, interval, call lists), ExtendHits, DeviceMakeSeeds
 //   api_rm.hip         repeat-masker entries and the device-side coverage post-processing
-//   api_gapped.hip     sa_gapped_extend / sa_gapped_align: gapped y-drop extension of HSP anchors and its paths (kernels: gapped.hip)
+//   api_gapped.hip     sa_gapped_extend / _align / _align_greedy: gapped extension of HSP anchors, paths, cover (gapped.hip, cover.hip)
 //   api_introspect.hip statistics, lookup mode, copies of device state for the tests
 #pragma once
 #include <hip/hip_runtime.h>

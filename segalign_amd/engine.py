@@ -354,67 +354,64 @@ def ExtendHits(hits, rev, buffer):
     return _take(n, out)[1:]
 
 
+def _flat(st):
+    """A stats struct as one dict, nested structs' fields inlined in order."""
+    out = {}
+    for k, _ in st._fields_:
+        v = getattr(st, k)
+        out.update(_flat(v) if isinstance(v, C.Structure) else {k: v})
+    return out
+
+
+def _gapped(fn, free, hsps, rev, buffer, params, st, *extra, paths=True):
+    """One call of a gapped entry on SEG_DTYPE hsps: -> (records, paths, ops) as arrays (paths=False: records alone), st filled."""
+    h = np.ascontiguousarray(hsps, dtype=SEG_DTYPE)
+    p = GappedParams(*(int(x) for x in params))
+    out, pth, ops, n_ops = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
+    tail = (C.byref(out), C.byref(pth), C.byref(ops), C.byref(n_ops)) if paths else (C.byref(out),)
+    n = fn(h.ctypes.data if h.size else None, h.size, int(bool(rev)), buffer, C.byref(p), *extra, *tail, C.byref(st))
+
+    def take(ptr, count, dtype):
+        if not count or not ptr.value:
+            return np.zeros(0, dtype=dtype)
+        return np.frombuffer((C.c_char * (count * dtype.itemsize)).from_address(ptr.value), dtype=dtype).copy()
+    recs = take(out, n, GAPPED_DTYPE)
+    if not paths:
+        free(out)
+        return recs
+    res = recs, take(pth, n, PATH_DTYPE), take(ops, n_ops.value, np.dtype("<u4"))
+    free(out, pth, ops)
+    return res
+
+
 def GappedExtend(hsps, rev, buffer, gap_open=400, gap_extend=30, ydrop=9430, gappedthresh=3000, max_extent=0, max_band=0, raw=False):
     """Gapped y-drop extension of HSP anchors on the device (sa_gapped_extend; contract in include/segalign_amd.h).
     hsps: SEG_DTYPE records (len = bases - 1) on strand `rev` of query `buffer`.  -> (GAPPED_DTYPE array, stats dict).
     raw: one record per HSP in input order; otherwise threshold, one record per extent, output order."""
-    h = np.ascontiguousarray(hsps, dtype=SEG_DTYPE)
-    p = GappedParams(int(gap_open), int(gap_extend), int(ydrop), int(gappedthresh), int(max_extent), int(max_band))
-    out = C.c_void_p()
     st = GappedStats()
-    n = lib().sa_gapped_extend(h.ctypes.data if h.size else None, h.size, int(bool(rev)), buffer, C.byref(p), int(bool(raw)),
-                               C.byref(out), C.byref(st))
-    recs = np.zeros(0, dtype=GAPPED_DTYPE)
-    if n and out.value:
-        recs = np.frombuffer((C.c_char * (n * GAPPED_DTYPE.itemsize)).from_address(out.value), dtype=GAPPED_DTYPE).copy()
-    if out.value:
-        lib().sa_free_gapped(out)
-    return recs, {k: getattr(st, k) for k, _ in GappedStats._fields_}
+    recs = _gapped(lib().sa_gapped_extend, lib().sa_free_gapped, hsps, rev, buffer,
+                   (gap_open, gap_extend, ydrop, gappedthresh, max_extent, max_band), st, int(bool(raw)), paths=False)
+    return recs, _flat(st)
 
 
 def GappedAlign(hsps, rev, buffer, gap_open=400, gap_extend=30, ydrop=9430, gappedthresh=3000, max_extent=0, max_band=0, raw=False):
     """GappedExtend plus the alignment path of every record (sa_gapped_align; contract in include/segalign_amd.h).
     -> (GAPPED_DTYPE records, PATH_DTYPE paths, uint32 ops, stats dict).  Record k's ops are
     ops[paths[k].op_offset:][:n_left + n_right], the left side's runs first; decode them with cigar()."""
-    h = np.ascontiguousarray(hsps, dtype=SEG_DTYPE)
-    p = GappedParams(int(gap_open), int(gap_extend), int(ydrop), int(gappedthresh), int(max_extent), int(max_band))
-    out, paths, ops, n_ops = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
     st = GappedAlignStats()
-    n = lib().sa_gapped_align(h.ctypes.data if h.size else None, h.size, int(bool(rev)), buffer, C.byref(p), int(bool(raw)),
-                              C.byref(out), C.byref(paths), C.byref(ops), C.byref(n_ops), C.byref(st))
-
-    def take(ptr, count, dtype):
-        if not count or not ptr.value:
-            return np.zeros(0, dtype=dtype)
-        return np.frombuffer((C.c_char * (count * dtype.itemsize)).from_address(ptr.value), dtype=dtype).copy()
-    recs, pth, o = take(out, n, GAPPED_DTYPE), take(paths, n, PATH_DTYPE), take(ops, n_ops.value, np.dtype("<u4"))
-    lib().sa_free_gapped_align(out, paths, ops)
-    stats = {k: getattr(st.extend, k) for k, _ in GappedStats._fields_}
-    stats.update({k: getattr(st, k) for k, _ in GappedAlignStats._fields_ if k != "extend"})
-    return recs, pth, o, stats
+    res = _gapped(lib().sa_gapped_align, lib().sa_free_gapped_align, hsps, rev, buffer,
+                  (gap_open, gap_extend, ydrop, gappedthresh, max_extent, max_band), st, int(bool(raw)))
+    return (*res, _flat(st))
 
 
 def GappedAlignGreedy(hsps, rev, buffer, gap_open=400, gap_extend=30, ydrop=9430, gappedthresh=3000, max_extent=0, max_band=0):
     """GappedAlign's records and paths, but anchors are extended best first and one that lies on an alignment accepted before it is
     skipped (sa_gapped_align_greedy; contract in include/segalign_amd.h).  -> (GAPPED_DTYPE records, PATH_DTYPE paths,
     uint32 ops, stats dict): GappedAlign's stats plus covered, below_thresh, skipped, priority_batches, cover_segments, cover_ms."""
-    h = np.ascontiguousarray(hsps, dtype=SEG_DTYPE)
-    p = GappedParams(int(gap_open), int(gap_extend), int(ydrop), int(gappedthresh), int(max_extent), int(max_band))
-    out, paths, ops, n_ops = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t()
     st = GappedGreedyStats()
-    n = lib().sa_gapped_align_greedy(h.ctypes.data if h.size else None, h.size, int(bool(rev)), buffer, C.byref(p), C.byref(out),
-                                     C.byref(paths), C.byref(ops), C.byref(n_ops), C.byref(st))
-
-    def take(ptr, count, dtype):
-        if not count or not ptr.value:
-            return np.zeros(0, dtype=dtype)
-        return np.frombuffer((C.c_char * (count * dtype.itemsize)).from_address(ptr.value), dtype=dtype).copy()
-    recs, pth, o = take(out, n, GAPPED_DTYPE), take(paths, n, PATH_DTYPE), take(ops, n_ops.value, np.dtype("<u4"))
-    lib().sa_free_gapped_align(out, paths, ops)
-    stats = {k: getattr(st.align.extend, k) for k, _ in GappedStats._fields_}
-    stats.update({k: getattr(st.align, k) for k, _ in GappedAlignStats._fields_ if k != "extend"})
-    stats.update({k: getattr(st, k) for k, _ in GappedGreedyStats._fields_ if k != "align"})
-    return recs, pth, o, stats
+    res = _gapped(lib().sa_gapped_align_greedy, lib().sa_free_gapped_align, hsps, rev, buffer,
+                  (gap_open, gap_extend, ydrop, gappedthresh, max_extent, max_band), st)
+    return (*res, _flat(st))
 
 
 def cigar(ops):
