@@ -239,6 +239,10 @@ int sa_max_hits_for_mem(uint64_t total_global_mem);
  *   gapped_greedy_edges  in-edges one resolve pass of sa_gapped_align_greedy holds (default 1 << 26, 4 bytes each; 1 .. 1 << 32).  Anchors
  *                     that cover each other pairwise give quadratically many; a batch with more is resolved in several passes, with the
  *                     same result.  Option debug prints the edge count of every call to stderr
+ *   gapped_pieces     pieces one side of sa_gapped_extend / sa_gapped_align / sa_gapped_align_greedy may take (default 1; 1 .. 1024).  A
+ *                     side that ends at max_extent is continued from its best cell by a fresh extension, piece after piece, and the
+ *                     pieces are joined into one record and one path ("Continuation pieces" below).  1: every entry
+ *                     returns what it returned before the option existed, bit for bit.  This option does change results
  * Launch geometry (defaults are the measured optima, tools/sweep_*.sh)
  *   fin_batch, bufs_per_wave, long_cap, long_blocks, max_waves, packed_waves, l2_blocks, ctx_waves, ctx_threads,
  *   chain_sort_threads, chain_sort_blocks, chain_group_max (candidates a chain workgroup sorts in LDS at a time), chain_bucket_target
@@ -372,9 +376,37 @@ size_t sa_order_hsps(const sa_segment_pair* in, size_t n, int rm, int path, sa_s
  *   hsp_index).  raw != 0: one record per input HSP in input order, no threshold, no de-duplication.
  * Not done here: LASTZ's skipping of anchors inside earlier alignments (redundant anchors are extended and removed by rule (2); the
  *   skipping is sa_gapped_align_greedy's, below), bit-identity with LASTZ.  The alignment path of each record (traceback) is
- *   sa_gapped_align's, below. */
-#define SA_GAPPED_EXTENT_CAP 1u /* a side reached max_extent bases */
+ *   sa_gapped_align's, below.
+ *
+ * Continuation pieces (option gapped_pieces = P, default 1; restated by tests/gapped_pieces_model.py).  Everything above
+ * describes one PIECE of a side; with P = 1 a side is its piece 0 and nothing below applies.
+ *   Piece 0 of a side is the extension above from the anchor.  Piece k yields (best_k, i_k, j_k, cells_k, flags_k) relative to its own
+ *   origin.  Piece k + 1 is run iff  k + 1 < P,  flags_k has SA_GAPPED_EXTENT_CAP and not SA_GAPPED_BAND_CAP,  (i_k, j_k) != (0, 0),  and
+ *   the side's running score best_0 + ... + best_k is below 1 << 29.
+ *   Origin of piece k + 1: the origin of piece k moved by (i_k, j_k) in the side's direction (right: +, left: -).  It is a fresh
+ *   extension -- H(0, 0) = 0, B_0 = 0 -- under the same dead-cell, y-drop, band, extent and best-cell rules, max_extent counted from the
+ *   new origin.  The cells beyond piece k's best cell that piece k explored are explored again by piece k + 1; that is intended.  The
+ *   y-drop state is not carried over, so a chain is not claimed to equal one uncapped extension.
+ *   Side: best = sum of best_k; extents = sum of i_k and sum of j_k; cells = sum of cells_k, saturating at 0xffffffff; flags =
+ *   the flags of the LAST piece (so SA_GAPPED_EXTENT_CAP now means "still truncated": the chain ended because P was reached, a later
+ *   piece made no progress, or the score limit), plus SA_GAPPED_CONTINUED when the side has more than one piece.  A chain also ends when
+ *   a piece does not reach max_extent: at a separator, the block's end, or by the y-drop.
+ *   Limit: a piece's best is at most max_extent x the largest sub_mat entry, which the limits above (max_extent <= 1 << 18, and the
+ *   int32 record score = left + right they already rely on) keep below 1 << 29; a piece is started only while the running score is
+ *   below 1 << 29, so a side stays below 1 << 30 and a record's score, the sum of two sides, inside int32.
+ *   Records, selection rules (1)-(3) and raw mode are unchanged, applied to the joined sides (a record's cells is still the 32-bit sum
+ *   of its two sides' cells).
+ *   Paths (sa_gapped_align): the pieces' ops in genome order -- left side: the last piece first, each piece in its walk order; right
+ *   side: piece 0 first, each piece reversed.  Runs are run-length inside a piece and NOT merged where two pieces meet, so two
+ *   adjacent runs may carry the same op there.  A junction is always M | anything: the best cell is the first to reach its score
+ *   (strict >), E and F only ever lose against the H they open from, so a best cell other than the origin is reached by an M step, and
+ *   every I or D run is still exactly one opened gap (O > 0).  Re-scoring a whole side -- sub_mat over its M pairs minus O + length x
+ *   E_ext per gap run -- gives the side's score; n_left / n_right count the runs of all pieces; matches ... gap_bases are sums.
+ *   Greedy (sa_gapped_align_greedy): the cover set of an alignment is the M pairs of all its pieces plus its anchor point; "bit-identical
+ *   to raw mode for that HSP" holds under the same gapped_pieces. */
+#define SA_GAPPED_EXTENT_CAP 1u /* a side reached max_extent bases (with gapped_pieces > 1: its last piece did) */
 #define SA_GAPPED_BAND_CAP 2u   /* a side ended at the band cap */
+#define SA_GAPPED_CONTINUED 4u  /* a side was continued past max_extent: it has more than one piece (option gapped_pieces) */
 
 typedef struct sa_gapped_params {
     int32_t gap_open;     /* O, default 400; 0 .. 1 << 20 */

@@ -1,8 +1,10 @@
 // api_gapped.hip -- C-ABI sa_gapped_extend: gapped y-drop extension of HSP anchors (contract: include/segalign_amd.h),
 // sa_gapped_align: the same records plus their alignment paths, sa_gapped_align_greedy: anchors on earlier alignments
-// skipped.  The host side as steps the entries share: the call frame, pass 1 (gapped.hip), the selection rules, trace
-// tasks, the trace batches sized from pass 1's best antidiagonals, the output; then greedy's cover index and resolve passes (cover.hip).
+// skipped.  The host side as steps the entries share: the call frame, pass 1 (gapped.hip), the continuation of sides that
+// ended at max_extent (option gapped_pieces), the selection rules, trace tasks, the trace batches sized from pass 1's
+// best antidiagonals, the output; then greedy's cover index and resolve passes (cover.hip).
 #include <functional>
+#include <unordered_map>
 
 #include "engine_internal.h"
 #include "gapped.h"
@@ -141,6 +143,19 @@ struct Point {
 Point anchor(const sa_segment_pair& h) { return {h.ref_start + h.len / 2, h.query_start + h.len / 2}; }
 uint64_t point_key(Point p, uint32_t query_len) { return (uint64_t)(p.t - p.q + query_len) << 32 | p.t; }
 
+// One piece of a continued side: its origin and its best cell relative to that origin.
+struct Piece {
+    uint32_t ar, aq;
+    int32_t best_i, best_j;
+};
+
+// Pass 1's results: HSP k's sides side[2 k] (left) and side[2 k + 1] (right).  A side that was continued (continue_sides) holds the
+// join of its pieces, and chain[its index] lists them, piece 0 first; a side of one piece has no chain.
+struct Sides {
+    std::vector<GappedSide> side;
+    std::unordered_map<size_t, std::vector<Piece>> chain;
+};
+
 // Pass 1: every HSP's two sides, side[2 k] and side[2 k + 1]; kernel time added to st.
 std::vector<GappedSide> extend_sides(Frame& f, const sa_segment_pair* hsps, size_t n, sa_gapped_stats& st) {
     Slot* sl = f.sl;
@@ -165,6 +180,78 @@ std::vector<GappedSide> extend_sides(Frame& f, const sa_segment_pair* hsps, size
         st.kernel_ms += tm.ms(0, 1);
     }
     return side;
+}
+
+// Continues the sides that ended at max_extent, piece after piece, up to option gapped_pieces pieces per side (the contract of
+// DESIGN.md 14 / include/segalign_amd.h).  Round r extends piece r of every side that still continues, in launches of the one-sided
+// kernel; the rounds end when none does.  With gapped_pieces = 1 nothing is launched and S.side stays pass 1's.
+void continue_sides(Frame& f, const sa_segment_pair* hsps, Sides& S, sa_gapped_stats& st) {
+    const int P = (int)g_gapped_pieces;
+    if (P <= 1) return;
+    struct Open {
+        size_t s;  // index in S.side
+        SideTask t;
+    };
+    auto continues = [&](const GappedSide& piece, size_t pieces, int32_t total) {
+        return pieces < (size_t)P && (piece.flags & SA_GAPPED_EXTENT_CAP) && !(piece.flags & SA_GAPPED_BAND_CAP) &&
+               (piece.best_i != 0 || piece.best_j != 0) && total < (1 << 29);
+    };
+    auto next_task = [](const SideTask& t, const GappedSide& g) {
+        return SideTask{t.dir > 0 ? t.ar + (uint32_t)g.best_i : t.ar - (uint32_t)g.best_i,
+                        t.dir > 0 ? t.aq + (uint32_t)g.best_j : t.aq - (uint32_t)g.best_j, t.dir, 0};
+    };
+    std::vector<Open> open, next;
+    for (size_t s = 0; s < S.side.size(); s++) {
+        const GappedSide& g = S.side[s];
+        if (!continues(g, 1, g.best)) continue;
+        const Point a = anchor(hsps[s / 2]);
+        const SideTask t0 = {a.t, a.q, (s & 1) ? 1 : -1, 0};
+        S.chain[s] = {{a.t, a.q, g.best_i, g.best_j}};
+        open.push_back({s, next_task(t0, g)});
+    }
+    if (open.empty()) return;
+    Slot* sl = f.sl;
+    const size_t continued = open.size(), batch = std::min(open.size(), 2 * GAPPED_BATCH);
+    SideTask* d_tasks;
+    GappedSide* d_side;
+    carve(sl->gapped, "gapped", [&](Carve& c) { c.take(d_tasks, batch).take(d_side, batch); });
+    Timer<2> tm(sl->stream);
+    std::vector<SideTask> tasks;
+    std::vector<GappedSide> res;
+    size_t pieces = 0, rounds = 0;
+    for (; !open.empty(); open.swap(next), rounds++) {
+        const size_t m = open.size();
+        tasks.resize(m);
+        res.resize(m);
+        for (size_t k = 0; k < m; k++) tasks[k] = open[k].t;
+        for (size_t b = 0; b < m; b += batch) {
+            const size_t c = std::min(batch, m - b);
+            check_memcpy(hipMemcpyAsync(d_tasks, tasks.data() + b, c * sizeof(SideTask), hipMemcpyHostToDevice, sl->stream), "gapped pieces");
+            tm.mark(0);
+            launch(sl, "gapped_pieces", [&] { launch_gapped_sides(f.a, d_tasks, (uint32_t)c, d_side, sl->stream); });
+            tm.mark(1);
+            check_memcpy(hipMemcpyAsync(res.data() + b, d_side, c * sizeof(GappedSide), hipMemcpyDeviceToHost, sl->stream), "gapped pieces");
+            check_sync(sl->stream, "gapped_pieces");
+            st.kernel_ms += tm.ms(0, 1);
+        }
+        next.clear();
+        for (size_t k = 0; k < m; k++) {
+            const Open& o = open[k];
+            const GappedSide& g = res[k];
+            GappedSide& J = S.side[o.s];
+            std::vector<Piece>& ch = S.chain[o.s];
+            ch.push_back({o.t.ar, o.t.aq, g.best_i, g.best_j});
+            J.best += g.best;
+            J.best_i += g.best_i;
+            J.best_j += g.best_j;
+            J.cells = (uint32_t)std::min<uint64_t>((uint64_t)J.cells + g.cells, 0xffffffffull);
+            J.flags = g.flags | SA_GAPPED_CONTINUED;  // the caps of the last piece: a cap that was continued past is no cap
+            if (continues(g, ch.size(), J.best)) next.push_back({o.s, next_task(o.t, g)});
+        }
+        pieces += m;
+    }
+    if (opt_value("debug"))
+        fprintf(stderr, "GappedPieces: %zu sides, %zu continued, %zu further pieces, %zu rounds\n", S.side.size(), continued, pieces, rounds);
 }
 
 // Selection rule (3): the output order of records.
@@ -224,32 +311,42 @@ std::vector<sa_gapped_alignment> make_records(const sa_segment_pair* hsps, size_
     return rec;
 }
 
-// Traced sides of records: record k's side s (0 left, 1 right) is task task_of[2 k + s] (-1: none), owned by record owner[t].  Once
-// walked, task t's runs in walk order are res[t].n_runs entries of runs from off[t] on.
+// Traced sides of records: record k's side s (0 left, 1 right) is the n_of[2 k + s] tasks from task_of[2 k + s] on (-1: none), one per
+// piece of the side with a best cell beyond its origin, in piece order; task t is owned by record owner[t].  Once walked, task t's
+// runs in walk order are res[t].n_runs entries of runs from off[t] on.
 struct Traces {
     std::vector<TraceTask> tasks;
     std::vector<int64_t> task_of;
+    std::vector<uint32_t> n_of;
     std::vector<uint32_t> owner, runs;
     std::vector<size_t> off;
     std::vector<TraceOut> res;
 };
 
-// The sides with a best cell beyond the anchor of the records scoring >= min_score, left before right; h = rec[k].hsp_index indexes
-// record k's HSP and sides.
-Traces trace_tasks(const std::vector<sa_gapped_alignment>& rec, const sa_segment_pair* hsps, const std::vector<GappedSide>& side,
-                   int min_score) {
+// The sides with a best cell beyond the anchor of the records scoring >= min_score, left before right, a continued side piece by
+// piece; h = rec[k].hsp_index indexes record k's HSP and sides.
+Traces trace_tasks(const std::vector<sa_gapped_alignment>& rec, const sa_segment_pair* hsps, const Sides& S, int min_score) {
     Traces tt;
     tt.task_of.assign(2 * rec.size(), -1);
+    tt.n_of.assign(2 * rec.size(), 0);
     for (size_t k = 0; k < rec.size(); k++) {
         if (rec[k].score < min_score) continue;
         const size_t h = rec[k].hsp_index;
         const Point a = anchor(hsps[h]);
         for (int s = 0; s < 2; s++) {
-            const GappedSide& g = side[2 * h + s];
+            const GappedSide& g = S.side[2 * h + s];
             if (g.best_i + g.best_j == 0) continue;
-            tt.task_of[2 * k + s] = (int64_t)tt.tasks.size();
-            tt.tasks.push_back({a.t, a.q, s ? 1 : -1, g.best_i + g.best_j, g.best_i, g.best_j, 0, 0});
-            tt.owner.push_back((uint32_t)k);
+            const size_t first = tt.tasks.size();
+            const auto ch = S.chain.find(2 * h + s);
+            if (ch == S.chain.end()) {
+                tt.tasks.push_back({a.t, a.q, s ? 1 : -1, g.best_i + g.best_j, g.best_i, g.best_j, 0, 0});
+            } else {
+                for (const Piece& p : ch->second)  // (only a chain's last piece can end at its own origin)
+                    if (p.best_i + p.best_j > 0) tt.tasks.push_back({p.ar, p.aq, s ? 1 : -1, p.best_i + p.best_j, p.best_i, p.best_j, 0, 0});
+            }
+            tt.task_of[2 * k + s] = (int64_t)first;
+            tt.n_of[2 * k + s] = (uint32_t)(tt.tasks.size() - first);
+            tt.owner.insert(tt.owner.end(), tt.tasks.size() - first, (uint32_t)k);
         }
     }
     return tt;
@@ -331,23 +428,28 @@ struct Output {
     std::vector<sa_gapped_alignment> rec;
     std::vector<sa_gapped_path> pa;
     std::vector<uint32_t> ops;
-    // the path of record k of tr: genome order, the left side's runs as walked, the right side's reversed
+    // the path of record k of tr: genome order, the left side's runs as walked, the right side's reversed; the pieces of a continued
+    // side in genome order too (left: the last piece first), their runs not merged where two pieces meet
     void add_path(const Traces& tr, size_t k) {
         sa_gapped_path g;
         memset(&g, 0, sizeof(g));
         g.op_offset = ops.size();
         for (int s = 0; s < 2; s++) {
-            const int64_t t = tr.task_of[2 * k + s];
-            if (t < 0) continue;
-            const TraceOut& o = tr.res[(size_t)t];
-            const uint32_t* w = tr.runs.data() + tr.off[(size_t)t];
-            if (s == 0) ops.insert(ops.end(), w, w + o.n_runs);
-            else for (uint32_t x = o.n_runs; x-- > 0;) ops.push_back(w[x]);
-            (s ? g.n_right : g.n_left) = o.n_runs;
-            g.matches += o.matches;
-            g.mismatches += o.mismatches;
-            g.gap_opens += o.gap_opens;
-            g.gap_bases += o.gap_bases;
+            const int64_t t0 = tr.task_of[2 * k + s];
+            if (t0 < 0) continue;
+            const uint32_t np = tr.n_of[2 * k + s];
+            for (uint32_t x = 0; x < np; x++) {
+                const size_t t = (size_t)t0 + (s == 0 ? np - 1 - x : x);
+                const TraceOut& o = tr.res[t];
+                const uint32_t* w = tr.runs.data() + tr.off[t];
+                if (s == 0) ops.insert(ops.end(), w, w + o.n_runs);
+                else for (uint32_t y = o.n_runs; y-- > 0;) ops.push_back(w[y]);
+                (s ? g.n_right : g.n_left) += o.n_runs;
+                g.matches += o.matches;
+                g.mismatches += o.mismatches;
+                g.gap_opens += o.gap_opens;
+                g.gap_bases += o.gap_bases;
+            }
         }
         pa.push_back(g);
     }
@@ -449,7 +551,8 @@ std::vector<uint32_t> survivors(Frame& f, CoverIndex& ix, const sa_segment_pair*
     return surv;
 }
 
-// trace_sides, each trace batch's segments emitted into the slot's cover_segs while its walk is on the device; returns their count.
+// trace_sides, each trace batch's segments emitted into the slot's cover_segs while its walk is on the device; returns their count.  A
+// piece of a continued side is a task of its own, so its runs are placed from the piece's origin and best cell, not the record's.
 size_t trace_emit(Frame& f, CoverIndex& ix, Traces& tr, sa_gapped_align_stats& st) {
     Slot* sl = f.sl;
     size_t nseg = 0;
@@ -600,9 +703,10 @@ size_t sa_gapped_extend(const sa_segment_pair* hsps, size_t n, int rev, uint32_t
     sa_gapped_stats st = {};
     Output o;
     if (n > 0) {
-        const std::vector<GappedSide> side = extend_sides(f, hsps, n, st);
+        Sides S = {extend_sides(f, hsps, n, st), {}};
+        continue_sides(f, hsps, S, st);
         f.release();
-        o.rec = make_records(hsps, n, side, f.P, raw, st);
+        o.rec = make_records(hsps, n, S.side, f.P, raw, st);
     }
     return o.hand_out(st, stats, out);
 }
@@ -615,9 +719,10 @@ size_t sa_gapped_align(const sa_segment_pair* hsps, size_t n, int rev, uint32_t 
     sa_gapped_align_stats st = {};
     Output o;
     if (n > 0) {
-        const std::vector<GappedSide> side = extend_sides(f, hsps, n, st.extend);
-        o.rec = make_records(hsps, n, side, f.P, raw, st.extend);
-        Traces tr = trace_tasks(o.rec, hsps, side, INT32_MIN);
+        Sides S = {extend_sides(f, hsps, n, st.extend), {}};
+        continue_sides(f, hsps, S, st.extend);
+        o.rec = make_records(hsps, n, S.side, f.P, raw, st.extend);
+        Traces tr = trace_tasks(o.rec, hsps, S, INT32_MIN);
         trace_sides(f, tr, st);
         f.release();
         o.pa.reserve(o.rec.size());
@@ -664,11 +769,12 @@ size_t sa_gapped_align_greedy(const sa_segment_pair* hsps, size_t n, int rev, ui
         // (2) extend the survivors (rank r = position in pi within the batch), trace the eligible ones' sides and emit their segments
         std::vector<sa_segment_pair> sh(S);
         for (size_t r = 0; r < S; r++) sh[r] = hsps[surv[r]];
-        const std::vector<GappedSide> side = extend_sides(f, sh.data(), S, st.align.extend);
-        const std::vector<sa_gapped_alignment> rec = make_records(sh.data(), S, side, f.P, 1, st.align.extend);
+        Sides sides = {extend_sides(f, sh.data(), S, st.align.extend), {}};
+        continue_sides(f, sh.data(), sides, st.align.extend);
+        const std::vector<sa_gapped_alignment> rec = make_records(sh.data(), S, sides.side, f.P, 1, st.align.extend);
         std::vector<uint8_t> elig(S);
         for (size_t r = 0; r < S; r++) elig[r] = rec[r].score >= f.P.gappedthresh;
-        Traces tr = trace_tasks(rec, sh.data(), side, f.P.gappedthresh);
+        Traces tr = trace_tasks(rec, sh.data(), sides, f.P.gappedthresh);
         const size_t nseg = trace_emit(f, ix, tr, st.align);
         // (3) edges between the survivors, (4) resolve, (5) the accepted segments into the index
         CoverWork w = cover_work(f, ix, sh, elig, nseg);

@@ -40,8 +40,9 @@ __device__ __forceinline__ uint32_t upper_bound64(const uint64_t* a, uint32_t n,
     return lo;
 }
 
-// One wave per side.  Walk order runs from the side's far end to the anchor: forward in the genome on the left side (from (a_r - best_i,
-// a_q - best_j)), backward on the right side (from (a_r + best_i, a_q + best_j)).  A wave prefix over the runs' target and query
+// One wave per traced side, or per piece of a continued side: (a_r, a_q) below is the task's own origin, so a piece's runs
+// are placed from that piece's origin and best cell, not from the record's start.  Walk order runs from the far end to the origin:
+// forward in the genome on the left side (from (a_r - best_i, a_q - best_j)), backward on the right side (from (a_r + best_i, a_q + best_j)).  A wave prefix over the runs' target and query
 // lengths places every run of a 64-run chunk; the chunk's totals carry into the next.
 __global__ void __launch_bounds__(256) cover_emit_kernel(const TraceTask* tasks, const TraceOut* out, const uint32_t* ops,
                                                          const CoverEmit* emit, uint32_t n, uint32_t query_len, CoverSeg* segs) {

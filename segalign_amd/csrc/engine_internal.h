@@ -243,6 +243,7 @@ constexpr int MAX_SLOTS_PER_DEVICE = 8;
 extern int64_t g_gapped_trace_mb;  // option gapped_trace_mb: MiB of trace area per sa_gapped_align batch
 extern int64_t g_gapped_greedy_batch;  // option gapped_greedy_batch: anchors per priority batch of sa_gapped_align_greedy
 extern int64_t g_gapped_greedy_edges;  // option gapped_greedy_edges: in-edges one resolve pass of sa_gapped_align_greedy holds
+extern int64_t g_gapped_pieces;  // option gapped_pieces: pieces a side of the gapped entries may take (1: no continuation)
 extern uint32_t SPEC_RECS;        // records of the speculative output copy (256 KB); option spec_recs (tests)
 extern uint32_t g_dedup_seg_max;  // option dedup_seg_max: records per segment the LDS chain accepts (0 = its LDS capacity; tests)
 constexpr int SA_MAX_CHUNKS = 256;  // chunks one multi-chunk call may carry: 2 reference iterations each = MAX_SEGS segments

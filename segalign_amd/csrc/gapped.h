@@ -31,9 +31,18 @@ struct GappedArgs {
 int gapped_cells_per_lane(int max_band);  // K of the kernel instance a band needs (64 K >= max_band + 1); -1: too wide
 void launch_gapped(const GappedArgs& a, hipStream_t s);
 
+// ---- continuation pieces (option gapped_pieces) ----
+struct SideTask {  // one one-sided extension from an explicit origin: a piece after a side's first
+    uint32_t ar, aq;  // origin (target, query): the previous piece's origin moved by its best cell
+    int32_t dir;      // -1 left, +1 right
+    uint32_t pad;
+};
+// Pass 1 of n such sides, one wave each: out[k] = the extension of tasks[k] (a.hsps, a.num_tasks and a.out are not read).
+void launch_gapped_sides(const GappedArgs& a, const SideTask* tasks, uint32_t n, GappedSide* out, hipStream_t s);
+
 // ---- trace sweep and path walk (sa_gapped_align) ----
-struct TraceTask {  // one side to trace: a side whose best cell is not the anchor
-    uint32_t ar, aq;     // anchor (a_r, a_q)
+struct TraceTask {  // one side to trace, or one piece of a continued side: its best cell is not its origin
+    uint32_t ar, aq;     // origin: the anchor (a_r, a_q), or a later piece's own origin
     int32_t dir;         // -1 left, +1 right
     int32_t dstar;       // best_i + best_j of the side (pass 1): the trace covers antidiagonals 1 .. dstar
     int32_t best_i, best_j;

@@ -262,6 +262,21 @@ __global__ __launch_bounds__(256) void gapped_kernel(GappedArgs a) {
     gapped_side<K, false>(a, s_sub, X, Y, a.out + task, nullptr, 0);
 }
 
+// Pass 1 of sides that start at an explicit origin (the continuation pieces of DESIGN.md 14): the same sweep, one wave per task.
+template <int K>
+__global__ __launch_bounds__(256) void gapped_sides_kernel(GappedArgs a, const SideTask* __restrict__ tasks, uint32_t n,
+                                                           GappedSide* __restrict__ out) {
+    __shared__ int s_sub[64];
+    if (threadIdx.x < 64) s_sub[threadIdx.x] = a.sub_mat[threadIdx.x];
+    __syncthreads();
+    const uint32_t task = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (task >= n) return;
+    const SideTask t = tasks[task];
+    const Seq X = {a.ref, (long long)a.ref_len, (long long)t.ar, t.dir};
+    const Seq Y = {a.query, (long long)a.query_len, (long long)t.aq, t.dir};
+    gapped_side<K, false>(a, s_sub, X, Y, out + task, nullptr, 0);
+}
+
 template <int K>
 __global__ __launch_bounds__(256) void gapped_trace_kernel(GappedArgs a, const TraceTask* __restrict__ tasks, uint32_t n, uint8_t* area) {
     __shared__ int s_sub[64];
@@ -435,6 +450,18 @@ void launch_gapped(const GappedArgs& a, hipStream_t s) {
         case 8: hipLaunchKernelGGL(gapped_kernel<8>, grid, block, 0, s, a); break;
         case 17: hipLaunchKernelGGL(gapped_kernel<17>, grid, block, 0, s, a); break;
         default: hipLaunchKernelGGL(gapped_kernel<33>, grid, block, 0, s, a); break;
+    }
+}
+
+void launch_gapped_sides(const GappedArgs& a, const SideTask* tasks, uint32_t n, GappedSide* out, hipStream_t s) {
+    if (n == 0) return;
+    const dim3 grid((n + 3) / 4), block(256);
+    switch (gapped_cells_per_lane(a.max_band)) {
+        case 2: hipLaunchKernelGGL(gapped_sides_kernel<2>, grid, block, 0, s, a, tasks, n, out); break;
+        case 4: hipLaunchKernelGGL(gapped_sides_kernel<4>, grid, block, 0, s, a, tasks, n, out); break;
+        case 8: hipLaunchKernelGGL(gapped_sides_kernel<8>, grid, block, 0, s, a, tasks, n, out); break;
+        case 17: hipLaunchKernelGGL(gapped_sides_kernel<17>, grid, block, 0, s, a, tasks, n, out); break;
+        default: hipLaunchKernelGGL(gapped_sides_kernel<33>, grid, block, 0, s, a, tasks, n, out); break;
     }
 }
 

@@ -69,6 +69,7 @@ int g_seed_upload = 0;  // option seed_upload: 0 pinned staging (memcpy + DMA), 
 int64_t g_gapped_trace_mb = 1024;  // option gapped_trace_mb (api_gapped.hip)
 int64_t g_gapped_greedy_batch = 1024;  // option gapped_greedy_batch (api_gapped.hip)
 int64_t g_gapped_greedy_edges = 1 << 26;  // option gapped_greedy_edges (api_gapped.hip)
+int64_t g_gapped_pieces = 1;  // option gapped_pieces (api_gapped.hip)
 
 // Class scores of the class filter (extend.hip 1d): cls[x] bounds every matrix entry a base pair with (target code ^ query
 // code) == x can have.  Codes >= 4 are stored as code 0 in the 2-bit copies, so a pair with such a code can show up in ANY
@@ -141,6 +142,7 @@ static Option g_opts[] = {
     {"gapped_trace_mb", 1024, 1, 1 << 20, 0},          // MiB of trace area sa_gapped_align packs the traced sides of one batch into; a larger side runs alone
     {"gapped_greedy_batch", 1024, 1, 1 << 20, 0},      // anchors per priority batch of sa_gapped_align_greedy (swept); results do not depend on it
     {"gapped_greedy_edges", 1 << 26, 1, 1ll << 32, 0}, // in-edges one resolve pass of sa_gapped_align_greedy holds (4 bytes each); a batch with more is resolved in several passes, with the same result
+    {"gapped_pieces", 1, 1, 1024, 0},                  // pieces a side of the gapped entries may take: a side that ends at max_extent is continued from its best cell; 1: never
     // launch geometry (swept by tools/sweep_*.sh; the defaults are the measured optima)
     {"fin_batch", 48, 1, 64, 0}, {"bufs_per_wave", 8, 1, 1 << 20, 0}, {"long_cap", 128, 0, 2 * PACK_PAD, 0},
     {"long_blocks", 1792, 1, 1 << 20, 0}, {"max_waves", 4096, 4, 1 << 20, 0}, {"packed_waves", 4096, 8, 1 << 20, 0},
@@ -221,6 +223,7 @@ void resolve_options() {
     g_gapped_trace_mb = opt_value("gapped_trace_mb");
     g_gapped_greedy_batch = opt_value("gapped_greedy_batch");
     g_gapped_greedy_edges = opt_value("gapped_greedy_edges");
+    g_gapped_pieces = opt_value("gapped_pieces");
     g_l2_cap_test = opt_value("l2_cap") ? (uint32_t)std::max<int64_t>(L2_NSUB, opt_value("l2_cap")) : 0u;
     g_spec_dedup = (int)opt_value("spec_dedup");
     SPEC_RECS = (uint32_t)opt_value("spec_recs");

@@ -48,7 +48,7 @@ PATH_KEY_ORDERED = 64
 
 GAPPED_DTYPE = np.dtype([("ref_start", "<u4"), ("ref_end", "<u4"), ("query_start", "<u4"), ("query_end", "<u4"), ("score", "<i4"),
                          ("hsp_index", "<u4"), ("flags", "<u4"), ("cells", "<u4")])  # sa_gapped_alignment
-GAPPED_EXTENT_CAP, GAPPED_BAND_CAP = 1, 2
+GAPPED_EXTENT_CAP, GAPPED_BAND_CAP, GAPPED_CONTINUED = 1, 2, 4
 
 
 class GappedParams(C.Structure):

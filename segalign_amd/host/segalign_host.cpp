@@ -40,6 +40,8 @@ struct Config {  // src/graph.h:32-76 with the defaults of src/main.cpp:61-124
     bool transition = true, noentropy = false, gapped = true, notrivial = false, debug = false, host_seeding = false;
     bool gpu_gapped = false;  // --gpu_gapped: a .gapped file next to every .segments file (sa_gapped_extend)
     bool gpu_maf = false;     // --gpu_maf (with --gpu_gapped): a .maf file of the same alignments next to every .gapped file (sa_gapped_align)
+    int gpu_pieces = 0;       // --gpu_pieces=N (with --gpu_gapped): engine option gapped_pieces, set before sa_initialize_processor; 0: left alone
+    uint32_t gpu_max_extent = 0;  // --gpu_max_extent=N (with --gpu_gapped): sa_gapped_params.max_extent; 0: the engine's default
     bool gpu_skip_covered = false;  // --gpu_skip_covered (with --gpu_gapped): the files hold sa_gapped_align_greedy's alignments
     int gap_open = 400, gap_extend = 30;
     int xdrop = 910, hspthresh = 3000, ydrop = 9430, gappedthresh = -1;
@@ -235,7 +237,7 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
         else for (size_t i = v.size(); i-- > 0;) emit(v[i]);  // :130: reverse vector order on the minus strand
         fclose(f);
         if (cfg.gpu_gapped) {  // the gapped extension of the same HSPs on the device: [start, end) extents printed like the segments
-            sa_gapped_params gp = {cfg.gap_open, cfg.gap_extend, cfg.ydrop, cfg.gappedthresh, 0, 0};
+            sa_gapped_params gp = {cfg.gap_open, cfg.gap_extend, cfg.ydrop, cfg.gappedthresh, cfg.gpu_max_extent, 0};
             sa_gapped_alignment* al = nullptr;
             sa_gapped_path* paths = nullptr;
             uint32_t* ops = nullptr;
@@ -316,7 +318,9 @@ static void usage() {
             "  --host-seeding (build seed vectors on the host like src/seeder.cpp) --debug\n"
             "  --gpu_gapped [--gap=O,E] (gapped y-drop extension on the GPU: a .gapped file next to each .segments file)\n"
             "  --gpu_maf (with --gpu_gapped: the alignments of each .gapped file as a .maf file in LASTZ's maf- layout)\n"
-            "  --gpu_skip_covered (with --gpu_gapped: extend anchors best first and skip those on earlier alignments)\n");
+            "  --gpu_skip_covered (with --gpu_gapped: extend anchors best first and skip those on earlier alignments)\n"
+            "  --gpu_max_extent=N (with --gpu_gapped: bases one piece of an alignment side may span; default 65536)\n"
+            "  --gpu_pieces=N (with --gpu_gapped: continue an alignment side that ends at the extent cap, up to N pieces; default 1)\n");
 }
 
 int main(int argc, char** argv) {
@@ -352,6 +356,11 @@ int main(int argc, char** argv) {
         else if (!strcmp(a, "--gpu_gapped")) cfg.gpu_gapped = true;
         else if (!strcmp(a, "--gpu_maf")) cfg.gpu_maf = true;
         else if (!strcmp(a, "--gpu_skip_covered")) cfg.gpu_skip_covered = true;
+        else if (opt(a, "--gpu_max_extent", v)) cfg.gpu_max_extent = (uint32_t)atol(v.c_str());
+        else if (opt(a, "--gpu_pieces", v)) {
+            cfg.gpu_pieces = atoi(v.c_str());
+            if (cfg.gpu_pieces < 1 || cfg.gpu_pieces > 1024) { fprintf(stderr, "bad --gpu_pieces=%s (1 .. 1024)\n", v.c_str()); return 1; }
+        }
         else if (opt(a, "--gap", v)) {
             if (sscanf(v.c_str(), "%d,%d", &cfg.gap_open, &cfg.gap_extend) != 2) { fprintf(stderr, "bad --gap=%s\n", v.c_str()); return 1; }
         }
@@ -388,6 +397,7 @@ int main(int argc, char** argv) {
         snprintf(slots, sizeof(slots), "%d", std::max(2, std::min(4, cfg.num_threads)));
         setenv("SEGALIGN_AMD_SLOTS", slots, 0);
     }
+    if (cfg.gpu_pieces > 0) sa_set_option("gapped_pieces", cfg.gpu_pieces);
     sa_initialize_processor(cfg.transition, cfg.wga_chunk, cfg.seed_size, sub_mat, cfg.xdrop, cfg.hspthresh, cfg.noentropy);  // :298
 
     auto t0 = std::chrono::steady_clock::now();

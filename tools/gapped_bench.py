@@ -5,7 +5,12 @@ the line then adds its extension, trace-sweep and walk ms, the trace bytes and b
 HSPs go through sa_gapped_align in selection mode and through sa_gapped_align_greedy: the line then adds, for both, the anchors
 extended, returned, covered, skipped and below threshold and the extension / trace / walk / cover ms.
 
+With --pieces N the engine runs with option gapped_pieces = N (sides that end at max_extent are continued), with
+--max-extent M the three entries get max_extent = M; the line then adds the sides continued, their further pieces and the rounds, the
+records still extent-capped or continued and the summed alignment length of each entry.
+
   python tools/gapped_bench.py [--workloads standin,lumpy] [--repeat 3] [--align] [--greedy] [--batches 1024,2048,...]
+                               [--pieces N] [--max-extent M]
 """
 import argparse
 import functools
@@ -68,6 +73,24 @@ def greedy_edges(text):
     return (int(m.group(2)), int(m.group(3)), int(m.group(1))) if m else (None, None, None)
 
 
+KW = {}  # max_extent for the three entries (--max-extent)
+
+
+def pieces_line(text):
+    """(sides continued, further pieces, rounds) summed over the lines option debug makes continue_sides print."""
+    tot = [0, 0, 0]
+    for m in re.finditer(r"GappedPieces: \d+ sides, (\d+) continued, (\d+) further pieces, (\d+) rounds", text):
+        for k in range(3):
+            tot[k] += int(m.group(k + 1))
+    return tot
+
+
+def span(recs):
+    """Summed target length of records, and how many are still extent-capped / were continued."""
+    return {"aligned_bases": int((recs["ref_end"].astype(np.int64) - recs["ref_start"]).sum()),
+            "still_capped": int(np.count_nonzero(recs["flags"] & 1)), "continued": int(np.count_nonzero(recs["flags"] & 4))}
+
+
 def greedy_fields(hsps, repeat, with_sel=True):
     """sa_gapped_align selection mode and sa_gapped_align_greedy on the same HSPs, the run with the least device time of each."""
     def best_of(f):
@@ -81,19 +104,24 @@ def greedy_fields(hsps, repeat, with_sel=True):
             if best is None or total < best[0]:
                 best = (total, r, wall)
         return best
-    g_total, (grecs, _, gops, gst), g_wall = best_of(lambda: E.GappedAlignGreedy(hsps, False, 0))
-    _, err = with_stderr(lambda: E.GappedAlignGreedy(hsps, False, 0))  # option debug is on: the call prints its edge count
+    g_total, (grecs, _, gops, gst), g_wall = best_of(lambda: E.GappedAlignGreedy(hsps, False, 0, **KW))
+    _, err = with_stderr(lambda: E.GappedAlignGreedy(hsps, False, 0, **KW))  # option debug is on: the call prints its edge count
     n_edges, max_edges, passes = greedy_edges(err)
     n = int(hsps.size)
     sel = {}
     s_total = None
     if with_sel:
-        s_total, (srecs, _, _, sst), s_wall = best_of(lambda: E.GappedAlign(hsps, False, 0))
-        below = int(np.count_nonzero(E.GappedExtend(hsps, False, 0, raw=True)[0]["score"] < 3000))
+        s_total, (srecs, _, _, sst), s_wall = best_of(lambda: E.GappedAlign(hsps, False, 0, **KW))
+        below = int(np.count_nonzero(E.GappedExtend(hsps, False, 0, raw=True, **KW)[0]["score"] < 3000))
         sel = {"sel_anchors": n, "sel_extended": int(sst["anchors"]), "sel_returned": int(srecs.size), "sel_below_thresh": below,
                "sel_extend_ms": round(sst["kernel_ms"], 3), "sel_trace_ms": round(sst["trace_ms"], 3), "sel_walk_ms": round(sst["walk_ms"], 3),
                "sel_kernel_ms": round(s_total, 3), "sel_call_ms": round(s_wall, 3), "sel_trace_bytes": int(sst["trace_bytes"]),
                "sel_trace_batches": int(sst["trace_batches"])}
+    if with_sel:
+        sel.update({"sel_" + k: v for k, v in span(srecs).items()})
+    sel.update({"greedy_" + k: v for k, v in span(grecs).items()})
+    gp = pieces_line(err)
+    sel.update({"greedy_sides_continued": gp[0], "greedy_further_pieces": gp[1]})
     return {**sel, "greedy_anchors": n, "greedy_extended": int(gst["anchors"]), "greedy_returned": int(grecs.size),
             "greedy_covered": int(gst["covered"]), "greedy_skipped": int(gst["skipped"]), "greedy_below_thresh": int(gst["below_thresh"]),
             "greedy_extend_ms": round(gst["kernel_ms"], 3), "greedy_trace_ms": round(gst["trace_ms"], 3),
@@ -106,10 +134,12 @@ def greedy_fields(hsps, repeat, with_sel=True):
             "trace_mb": int(E.get_option("gapped_trace_mb")), "greedy_ops": int(gops.size)}
 
 
-def run(name, repeat, align=False, greedy=False, with_sel=True):
+def run(name, repeat, align=False, greedy=False, with_sel=True, pieces=0):
     t, q = workload(name)
-    if greedy:
-        E.set_option("debug", 1)  # sa_gapped_align_greedy then prints its edge count
+    if greedy or pieces:
+        E.set_option("debug", 1)  # sa_gapped_align_greedy then prints its edge count, the continuation its pieces
+    if pieces:
+        E.set_option("gapped_pieces", pieces)
     E.InitializeInterface(1)
     E.GenerateShapePos(SHAPE)
     E.InitializeProcessor(True, 250_000, 19, SUB, 910, 3000, False)
@@ -122,17 +152,22 @@ def run(name, repeat, align=False, greedy=False, with_sel=True):
     best = None
     for _ in range(repeat):
         t0 = time.perf_counter()
-        recs, st = E.GappedExtend(hsps, False, 0)
+        recs, st = E.GappedExtend(hsps, False, 0, **KW)
         wall = (time.perf_counter() - t0) * 1e3
         if best is None or st["kernel_ms"] < best[1]["kernel_ms"]:
             best = (recs, st, wall)
     recs, st, wall = best
     extra = {}
+    if pieces:
+        _, err = with_stderr(lambda: E.GappedExtend(hsps, False, 0, **KW))
+        pc = pieces_line(err)
+        extra = {"pieces": pieces, "max_extent": KW.get("max_extent", 65536), "sides_continued": pc[0], "further_pieces": pc[1],
+                 "rounds": pc[2], "pieces_per_continued_side": round(1 + pc[1] / pc[0], 3) if pc[0] else None, **span(recs)}
     if align:
         best_a = None
         for _ in range(repeat):
             t0 = time.perf_counter()
-            arecs, paths, ops, ast = E.GappedAlign(hsps, False, 0)
+            arecs, paths, ops, ast = E.GappedAlign(hsps, False, 0, **KW)
             awall = (time.perf_counter() - t0) * 1e3
             total = ast["kernel_ms"] + ast["trace_ms"] + ast["walk_ms"]
             if best_a is None or total < best_a[0]:
@@ -140,15 +175,17 @@ def run(name, repeat, align=False, greedy=False, with_sel=True):
         total, arecs, ops, ast, awall = best_a
         if not np.array_equal(arecs, recs):
             raise SystemExit("sa_gapped_align returned other records than sa_gapped_extend")
-        extra = {"align_extend_ms": round(ast["kernel_ms"], 3), "align_trace_ms": round(ast["trace_ms"], 3),
+        extra.update({"align_extend_ms": round(ast["kernel_ms"], 3), "align_trace_ms": round(ast["trace_ms"], 3),
                  "align_walk_ms": round(ast["walk_ms"], 3), "align_kernel_ms": round(total, 3), "align_call_ms": round(awall, 3),
                  "align_over_extend": round(total / st["kernel_ms"], 3) if st["kernel_ms"] > 0 else None,
-                 "trace_bytes": int(ast["trace_bytes"]), "trace_batches": int(ast["trace_batches"]), "ops": int(ops.size)}
+                 "trace_bytes": int(ast["trace_bytes"]), "trace_batches": int(ast["trace_batches"]), "ops": int(ops.size)})
     if greedy:
         extra.update(greedy_fields(hsps, repeat, with_sel))
     E.ShutdownProcessor()
-    if greedy:
+    if greedy or pieces:
         E.reset_option("debug")
+    if pieces:
+        E.reset_option("gapped_pieces")
     return {"workload": name, "call": list(call), "anchors": int(st["anchors"]), "alignments": int(st["returned"]),
             "cells": int(st["cells"]), "cells_per_anchor": st["cells"] / max(st["anchors"], 1),
             "extent_capped": int(st["extent_capped"]), "band_capped": int(st["band_capped"]),
@@ -163,14 +200,18 @@ def main():
     ap.add_argument("--align", action="store_true", help="also time sa_gapped_align on the same HSPs")
     ap.add_argument("--greedy", action="store_true", help="also time sa_gapped_align (selection mode) and sa_gapped_align_greedy")
     ap.add_argument("--batches", default="", help="with --greedy: one line per gapped_greedy_batch value, greedy only (a sweep)")
+    ap.add_argument("--pieces", type=int, default=0, help="engine option gapped_pieces (0: left at its default of 1)")
+    ap.add_argument("--max-extent", type=int, default=0, help="max_extent of every entry (0: the default, 65536)")
     a = ap.parse_args()
+    if a.max_extent:
+        KW["max_extent"] = a.max_extent
     for name in a.workloads.split(","):
         if not a.batches:
-            print(json.dumps(run(name, a.repeat, a.align, a.greedy)), flush=True)
+            print(json.dumps(run(name, a.repeat, a.align, a.greedy, pieces=a.pieces)), flush=True)
             continue
         for b in a.batches.split(","):
             E.set_option("gapped_greedy_batch", int(b))
-            print(json.dumps(run(name, a.repeat, a.align, True, with_sel=False)), flush=True)
+            print(json.dumps(run(name, a.repeat, a.align, True, with_sel=False, pieces=a.pieces)), flush=True)
         E.reset_option("gapped_greedy_batch")
 
 
