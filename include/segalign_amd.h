@@ -221,7 +221,6 @@ int sa_max_hits_for_mem(uint64_t total_global_mem);
  *                     beforehand (e.g. 180 for 500 Mbp blocks) takes the allocation off the table build's critical path
  *   clear_ref_frees   1: g_ClearRef frees the index / position / extent tables like the reference's clearRef (seed_filter_interface.cu:103-113);
  *                     0 (default): it forgets the tables and keeps their buffers for the next target block (ShutdownProcessor frees them)
- *   key_order, key_order_chunks, key_order_hits, key_order_min_pos   key-ordered calls (off by default)
  *   ctx_skip_seed, table_scratch_arena, log4_double                  INTEGRATION.md 4
  *   l2_right_state    1: the second filter level resumes an open RIGHT walk behind the class filter's context from its packed state
  *                     (default 0: measured without effect, profiles/r06/ab_l2state_prio.txt)
@@ -290,7 +289,7 @@ typedef struct sa_call_stats {
 #define SA_PATH_CHAIN_BUCKET_OVERFLOW 4u /* a chain bucket above its LDS capacity was left unsorted (costs extensions, never results) */
 #define SA_PATH_CHAIN_SLICED 8u          /* more candidates than the chain buffers hold: the chain stages ran over the list slice by slice */
 #define SA_PATH_HEAD_BITS_REGROWN 16u    /* the head-bit map of the call's hits was regrown and the compaction repeated */
-#define SA_PATH_KEY_ORDERED 64u          /* the call ran key-ordered: positions sorted by seed key, hits enumerated per key (join.h) */
+/* bit 64u is retired (it was SA_PATH_KEY_ORDERED): never set, and no other flag takes its place */
 #define SA_PATH_GENERAL_FALLBACK 32u     /* a device-seeded call could not take the table-direct path (a chunk of 6 x MAX_HITS hits or more, > 2^32 hits, ...) */
 void sa_get_last_call_stats(sa_call_stats* out); /* stats of the calling thread's most recent hot call */
 void sa_set_count_examined(int on);

@@ -36,7 +36,6 @@
 #include "kernels.h"
 #include "plan.h"
 #include "probe.h"
-#include "join.h"
 
 namespace sa {
 
@@ -246,9 +245,10 @@ extern int64_t g_gapped_greedy_edges;  // option gapped_greedy_edges: in-edges o
 extern int64_t g_gapped_pieces;  // option gapped_pieces: pieces a side of the gapped entries may take (1: no continuation)
 extern uint32_t SPEC_RECS;        // records of the speculative output copy (256 KB); option spec_recs (tests)
 extern uint32_t g_dedup_seg_max;  // option dedup_seg_max: records per segment the LDS chain accepts (0 = its LDS capacity; tests)
-constexpr int SA_MAX_CHUNKS = 256;  // chunks one multi-chunk call may carry: 2 reference iterations each = MAX_SEGS segments
-static_assert(SA_MAX_CHUNKS == (int)JOIN_SEG_FIRST && 2 * SA_MAX_CHUNKS <= MAX_SEGS,
-              "a call's chunks x 2 reference iterations = MAX_SEGS segments (d_seg_end holds MAX_SEGS u64); the join path's segment table (join.h) is cut at SA_MAX_CHUNKS");
+constexpr int SA_MAX_CHUNKS = 256;  // chunks one multi-chunk call may carry.  A chunk below MAX_HITS is planned in 2 reference iterations, a table-direct
+                                    // chunk above it in up to TD_MAX_ITER: td_front's runtime check keeps a call's sum within MAX_SEGS (else the pass is halved)
+static_assert(2 * SA_MAX_CHUNKS <= MAX_SEGS,
+              "a full call of chunks below MAX_HITS (2 reference iterations each) fits the MAX_SEGS segments one extension batch resolves (d_seg_end holds MAX_SEGS u64)");
 constexpr int SA_MAX_CHUNKS_GENERAL = 32;  // ... when it takes the general path (per-chunk iteration plans of up to 1000 iterations each)
 constexpr int SA_DEFAULT_CHUNKS = 40;  // ... and what the interval entries hand to one call: the 40 chunks of a strand of a 10 Mbp interval
 extern int SLOTS_PER_DEVICE;  // calls in flight per device (the reference allows one: token == device); option slots
@@ -328,15 +328,6 @@ struct Slot {
     std::vector<ProfRec> prof_pending;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> event_pool;
     size_t events_used = 0;
-    // key-ordered calls (join.h / join.hip): the call's positions sorted by key, entries by class, the query field words
-    DevBuf<uint32_t> jq_keys, jq_pairs, jq_misc, jq_start, jq_pos, jq_ent_nt, jq_qx;
-    DevBuf<uint4> jq_ent;
-    DevBuf<unsigned long long> jq_vstart, jq_stats;
-    DevBuf<uint8_t> jq_scan;
-    JoinHead* d_jhead = nullptr;
-    JoinChunk* d_jplan = nullptr;
-    JoinChunk* h_jplan = nullptr;     // pinned
-    uint32_t jq_chunk = 0;            // chunk size of the running key-ordered call
     WorkRegion work;                  // this slot's share of the device's work arena
     DevBuf<uint8_t> gapped;           // sa_gapped_extend: a batch's HSPs and its per-side results (api_gapped.hip)
     DevBuf<uint8_t> gapped_trace;     // sa_gapped_align: a batch's side tasks, walk results, op areas and trace areas (api_gapped.hip)
@@ -468,8 +459,6 @@ extern int g_fast_filter;
 extern int g_packed_filter;
 extern int g_chain_sort_threads, g_chain_buckets, g_chain_bucket_target, g_chain_sort_blocks, g_chain_group_max;
 extern int g_chunks_per_call;
-extern int g_key_order, g_key_order_chunks;
-extern int64_t g_key_order_hits, g_key_order_min_pos;
 extern int64_t g_call_hits, g_call_hits_max;
 extern int g_no_small_dedup;
 extern int g_ctx;
@@ -562,7 +551,6 @@ struct CoreArgs {
     const PackedBuf* q2_own;
     const PackedBuf* q2_other;
     uint32_t q_present;
-    int join;                             // key-ordered call (join_front has sorted the positions and planned the chunks): td is set as well
 };
 
 size_t saf_core(DevCtx* dc, Slot* sl, uint32_t num_seeds, const CoreArgs& ca, sa_segment_pair** out);
@@ -577,9 +565,6 @@ bool ensure_nbr(DevCtx* dc);
 bool q2_usable(const PackedBuf* q2_own, const PackedBuf* q2_other);
 bool td_eligible(DevCtx* dc, const PackedBuf* query4, const PackedBuf* q2_own, const PackedBuf* q2_other);
 uint32_t td_front(DevCtx* dc, Slot* sl, const uint8_t* qcodes, int K, const uint32_t* bpos, int rm, uint32_t* words_out);
-bool join_wanted(DevCtx* dc, int K, uint32_t n_positions);  // should this call take the key-ordered form?
-uint32_t join_front(DevCtx* dc, Slot* sl, const uint8_t* qcodes, uint32_t qlen, int K, const uint32_t* bpos, const PackedBuf* q2_own, const PackedBuf* q2_other,
-                    uint32_t* words_out);
 uint32_t dropin_td_front(DevCtx* dc, Slot* sl, const uint8_t* qcodes, uint32_t qlen, const uint64_t* host_seeds, size_t n,
                          const PackedBuf* q4, const PackedBuf* q2_own, const PackedBuf* q2_other, int rm, uint32_t* first_out,
                          uint32_t* end_out, uint32_t* words_out);

@@ -13,7 +13,8 @@ namespace sa {
 constexpr int SEQ_PAD = 64;
 
 constexpr int MAX_CARE = 16;  // seed weight limit; reference asserts 3 < kmer_size <= 15 (seed_pos_table.cu:51-52)
-constexpr int MAX_SEGS = 512;  // reference iterations handled by one extension batch (256 chunks x 2 iterations of a table-direct call)
+constexpr int MAX_SEGS = 512;  // reference iterations handled by one extension batch: a table-direct chunk contributes 2, or up to TD_MAX_ITER (probe.h)
+                               // at or above MAX_HITS; td_front's runtime check keeps a call's sum within MAX_SEGS
 constexpr int MAX_SEGS_ABS = 8;  // ... of a batch whose chain sort key carries absolute query positions (general path)
 
 struct SeedShape {            // device copy of the state GenerateShapePos keeps (ntcoding.cpp:6-8)
@@ -200,11 +201,6 @@ struct ExtendArgs {
     uint32_t out_cap;         // capacity of out[]; the counter keeps counting past it, writes are dropped
     uint32_t* out_count;      // device counter
     unsigned long long* examined; // optional (null = do not count): [0] = E of the call, [1] = bases scored by the filter
-    // key-ordered call (join.h): hits carry no index -- seg_end points at the per-chunk table join_plan_kernel wrote ({p_last : e_thr}
-    // x 256, then the chunks' first segments x 256), L2Rec / CandRec::hidx is the hit's entry index inside its key's run
-    int join;
-    uint32_t join_q_lo;       // first query position of the call
-    uint32_t join_chunk;      // chunk size (wga_chunk)
     // repeat-masker deltas (repeat_masker_src/seed_filter.cu:239-244, 305-333, 705-708)
     int rm;
     uint32_t rm_win_start, rm_win_end;

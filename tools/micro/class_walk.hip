@@ -11,7 +11,7 @@
 //   C  per 4 banks:  1024 entries (5 bases) x 8 copies, copy r on banks 4r .. 4r+3  32 KB   23 lookups per hit   4 lanes share 4 banks
 // Every variant runs twice: LDS ONLY (the reads and one xor each: the LDS cycles per 64 hits) and as the WALK (address extraction from
 // the seven class-string dwords, cls_step with W as in the filter, the verdict's few ops) -- no global memory in either, so what is
-// measured is the CU's LDS + VALU issue, the two units the key-ordered filter is bound by.
+// measured is the CU's LDS + VALU issue, the two units the key-ordered filter was bound by.
 // Class strings come from a per-lane additive generator (7 VALU per hit, the same in every variant).
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -o class_walk class_walk.hip
 #include <hip/hip_runtime.h>

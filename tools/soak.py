@@ -64,9 +64,6 @@ def one_case(seed, s14):
     if shape:
         kw["shape"] = shape
     E.reset_option(None)
-    ko = bool(rng.random() < 0.3)   # the multi-chunk calls of (2) key-ordered (option key_order = 2: join.hip, extend.hip 1e)
-    if ko:
-        E.set_option("key_order", 2)
     audit = bool(rng.random() < 0.3)  # every hit the filter levels REJECT in the per-chunk calls of (1) extended by the oracle: none may pass
     if audit:
         E.set_option("audit_cap", 1 << 22)
@@ -83,7 +80,6 @@ def one_case(seed, s14):
         mh = max(mh, max(per + [0]) // 500 + 1)
     E.set_max_hits(mh if mh < (1 << 30) else 0)
     kw["max_hits"] = mh
-    kw["key_order"] = ko
     kw["audit"] = audit
     hsps = hits = 0
     audited = [0]
@@ -147,7 +143,7 @@ def main():
             sys.exit(1)
         print("seed %d %-9s %7d bp step %d %s chunk %6d xdrop %4d thresh %4d %s%s: %d hits, %d HSPs ok" % (
             seed, kind, size, kw["step"], "tr" if kw["transition"] else "no-tr", kw["chunk"], kw["xdrop"], kw["hspthresh"],
-            "noentropy " if kw["noentropy"] else "", ("14of22" if "shape" in kw else "12of19") + (" key-ordered" if kw.get("key_order") else "") + (" audited %d" % kw["audited"] if kw.get("audit") else "") + (" MAX_HITS %d" % kw["max_hits"] if kw["max_hits"] < (1 << 30) else ""), hits, hsps), flush=True)
+            "noentropy " if kw["noentropy"] else "", ("14of22" if "shape" in kw else "12of19") + (" audited %d" % kw["audited"] if kw.get("audit") else "") + (" MAX_HITS %d" % kw["max_hits"] if kw["max_hits"] < (1 << 30) else ""), hits, hsps), flush=True)
         n += 1
         tot_hits += hits
         tot_hsps += hsps
