@@ -5,6 +5,10 @@
  * every antidiagonal up to the side's end, and then walks back from the best cell to the anchor comparing VALUES under the tie rules
  * of the contract (the engine compares stored bits).  The tests hold its results against gapped_check.c's records, an unpruned
  * full-matrix Gotoh traceback, hand-worked cases and every path the engine returns.
+ *
+ * GT_VARIANT (compile-time, default 0 = the contract) builds a deliberately WRONG checker, used only to show that an input's result
+ * hangs on a tie rule (tests/test_gapped_regimes.py): 1 = the source of H is taken F before E before M; 2 = of the cells of one
+ * antidiagonal that reach a new maximum the last one (largest i) is the best cell, not the first.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -17,6 +21,9 @@
 #define OP_M 0u
 #define OP_I 1u
 #define OP_D 2u
+#ifndef GT_VARIANT
+#define GT_VARIANT 0
+#endif
 
 typedef struct {
     int32_t best, best_i, best_j;
@@ -97,7 +104,11 @@ void gt_side(const uint8_t* t, int64_t tlen, const uint8_t* q, int64_t qlen, con
                 if (i < nlo) nlo = i;
                 nhi = i;
                 dcells++;
+#if GT_VARIANT == 2
+                if (h >= dbest) { dbest = h; dbest_i = i; }
+#else
                 if (h > dbest) { dbest = h; dbest_i = i; }
+#endif
                 if (i == max_extent || j == max_extent) dflags |= FLAG_EXTENT;
             } else {
                 h = e = f = NEG;
@@ -139,6 +150,13 @@ void gt_side(const uint8_t* t, int64_t tlen, const uint8_t* q, int64_t qlen, con
             int32_t m = NEG;
             const int x = X_AT(i), y = Y_AT(j);
             if (i >= 1 && j >= 1) m = max2(val(D, nd, d - 2, i - 1, 0) + sub[x * 8 + y], NEG);
+#if GT_VARIANT == 1
+            if (h == val(D, nd, d, i, 2)) {
+                st = 2;
+            } else if (h == val(D, nd, d, i, 1)) {
+                st = 1;
+            } else
+#endif
             if (i >= 1 && j >= 1 && h == m) {
                 EMIT(OP_M);
                 score += sub[x * 8 + y];

@@ -18,7 +18,7 @@ PATH_DTYPE = np.dtype([("op_offset", "<u8"), ("n_left", "<u4"), ("n_right", "<u4
                        ("gap_opens", "<u4"), ("gap_bases", "<u4")])
 OP_M, OP_I, OP_D = 0, 1, 2
 
-_lib = None
+_libs = {}
 
 
 class SideResult(C.Structure):
@@ -30,32 +30,33 @@ class Walk(C.Structure):
                 ("gap_bases", C.c_uint32), ("score", C.c_int32), ("err", C.c_int32)]
 
 
-def lib():
-    global _lib
-    if _lib is None:
+def lib(variant=0):
+    """The checker; variant != 0: the deliberately wrong build GT_VARIANT = variant (see the C file), for tie-sensitivity checks only."""
+    if variant not in _libs:
         cc = os.environ.get("CC") or shutil.which("cc") or shutil.which("gcc")
         d = tempfile.mkdtemp(prefix="gapped_trace_check_")
         so = os.path.join(d, "libgapped_trace_check.so")
-        subprocess.check_call([cc, "-O2", "-std=c99", "-Wall", "-shared", "-fPIC", SRC, "-o", so])
+        subprocess.check_call([cc, "-O2", "-std=c99", "-Wall", "-shared", "-fPIC", "-DGT_VARIANT=%d" % variant, SRC, "-o", so])
         L = C.CDLL(so)
         L.gt_side.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
                               C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(SideResult), C.c_void_p, C.POINTER(Walk)]
-        _lib = L
-    return _lib
+        _libs[variant] = L
+    return _libs[variant]
 
 
 def _u8(a):
     return np.ascontiguousarray(a, dtype=np.uint8)
 
 
-def side(t, q, sub, ar, aq, direction, gap_open=400, gap_extend=30, ydrop=9430, max_extent=G.DEFAULT_EXTENT, max_band=G.DEFAULT_BAND):
+def side(t, q, sub, ar, aq, direction, gap_open=400, gap_extend=30, ydrop=9430, max_extent=G.DEFAULT_EXTENT, max_band=G.DEFAULT_BAND,
+         variant=0):
     """One side: -> ((best, best_i, best_j, cells, flags), ops in walk order (uint32 array), walk dict)."""
     t, q = _u8(t), _u8(q)
     m = np.ascontiguousarray(sub, dtype=np.int32)
     r, w = SideResult(), Walk()
     ops = np.zeros(2 * max_extent + 2, dtype=np.uint32)
-    lib().gt_side(t.ctypes.data, t.size, q.ctypes.data, q.size, m.ctypes.data, int(ar), int(aq), int(direction), gap_open, gap_extend,
-                  ydrop, max_extent, max_band, C.byref(r), ops.ctypes.data, C.byref(w))
+    lib(variant).gt_side(t.ctypes.data, t.size, q.ctypes.data, q.size, m.ctypes.data, int(ar), int(aq), int(direction), gap_open, gap_extend,
+                         ydrop, max_extent, max_band, C.byref(r), ops.ctypes.data, C.byref(w))
     walk = {k: getattr(w, k) for k, _ in Walk._fields_}
     assert walk["err"] == 0, walk
     return (r.best, r.best_i, r.best_j, r.cells, r.flags), ops[:w.n_ops].copy(), walk

@@ -41,9 +41,10 @@ def sample(h, k):
     return h[np.linspace(0, h.size - 1, min(k, h.size)).astype(np.int64)] if h.size else h
 
 
-def check_raw(E, ref, qcodes, hsps, rev, buf, **kw):
+def check_raw(E, ref, qcodes, hsps, rev, buf, sub=SUB, **kw):
+    """Every field of every raw record, and the call's statistics, against gapped_check.c (sub: the matrix the engine was started with)."""
     got, st = E.GappedExtend(hsps, rev, buf, raw=True, **kw)
-    want = G.extend(ref, qcodes, SUB, hsps, **{k: v for k, v in kw.items() if k != "gappedthresh"})
+    want = G.extend(ref, qcodes, sub, hsps, **{k: v for k, v in kw.items() if k != "gappedthresh"})
     assert got.size == want.size == hsps.size
     bad = np.nonzero(got != want)[0]
     assert bad.size == 0, (kw, got[bad[:3]].tolist(), want[bad[:3]].tolist())

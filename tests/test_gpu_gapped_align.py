@@ -47,8 +47,8 @@ def sample(h, k):
     return h[np.linspace(0, h.size - 1, min(k, h.size)).astype(np.int64)] if h.size else h
 
 
-def check_paths(ref, q, hsps, recs, paths, ops, gap_open=400, gap_extend=30):
-    """The path invariants of the contract on every record."""
+def check_paths(ref, q, hsps, recs, paths, ops, gap_open=400, gap_extend=30, sub=SUB):
+    """The path invariants of the contract on every record (sub: the matrix the engine was started with)."""
     assert paths.size == recs.size
     total = 0
     for k in range(recs.size):
@@ -61,8 +61,8 @@ def check_paths(ref, q, hsps, recs, paths, ops, gap_open=400, gap_extend=30):
         assert T.canonical(lo) and T.canonical(ro)
         assert T.consumed(lo) == (ar - int(r["ref_start"]), aq - int(r["query_start"]))
         assert T.consumed(ro) == (int(r["ref_end"]) - ar, int(r["query_end"]) - aq)
-        sl, ml, xl = T.rescore(ref, q, SUB, int(r["ref_start"]), int(r["query_start"]), lo, gap_open, gap_extend)
-        sr, mr, xr = T.rescore(ref, q, SUB, ar, aq, ro, gap_open, gap_extend)
+        sl, ml, xl = T.rescore(ref, q, sub, int(r["ref_start"]), int(r["query_start"]), lo, gap_open, gap_extend)
+        sr, mr, xr = T.rescore(ref, q, sub, ar, aq, ro, gap_open, gap_extend)
         assert sl + sr == int(r["score"])
         assert (ml + mr, xl + xr) == (int(p["matches"]), int(p["mismatches"]))
         gaps = np.concatenate([lo, ro])
@@ -71,14 +71,14 @@ def check_paths(ref, q, hsps, recs, paths, ops, gap_open=400, gap_extend=30):
     assert total == ops.size
 
 
-def check_align(E, ref, q, hsps, rev, buf, raw=True, **kw):
+def check_align(E, ref, q, hsps, rev, buf, raw=True, sub=SUB, **kw):
     recs, paths, ops, st = E.GappedAlign(hsps, rev, buf, raw=raw, **kw)
     ext, est = E.GappedExtend(hsps, rev, buf, raw=raw, **kw)
     assert recs.size == ext.size and np.array_equal(recs, ext)
     for k in ("anchors", "cells", "extent_capped", "band_capped", "returned"):
         assert st[k] == est[k], k
     mk = {k: v for k, v in kw.items() if k != "gappedthresh"}
-    raw_want, want_paths = T.align(ref, q, SUB, hsps, **mk)
+    raw_want, want_paths = T.align(ref, q, sub, hsps, **mk)
     if raw:
         assert np.array_equal(recs, raw_want)
         sel_paths = want_paths
@@ -88,7 +88,7 @@ def check_align(E, ref, q, hsps, rev, buf, raw=True, **kw):
     wp, wops = T.pack(sel_paths)
     assert np.array_equal(paths, wp), (paths[:3], wp[:3])
     assert np.array_equal(ops, wops)
-    check_paths(ref, q, hsps, recs, paths, ops, kw.get("gap_open", 400), kw.get("gap_extend", 30))
+    check_paths(ref, q, hsps, recs, paths, ops, kw.get("gap_open", 400), kw.get("gap_extend", 30), sub)
     if recs.size:
         assert st["trace_batches"] >= 1 and st["trace_bytes"] > 0
     return recs, paths, ops, st
