@@ -242,6 +242,8 @@ int sa_max_hits_for_mem(uint64_t total_global_mem);
  *                     side that ends at max_extent is continued from its best cell by a fresh extension, piece after piece, and the
  *                     pieces are joined into one record and one path ("Continuation pieces" below).  1: every entry
  *                     returns what it returned before the option existed, bit for bit.  This option does change results
+ *   chain_tile        HSPs per tile of sa_chain_hsps (default 256; a power of two, 64 .. 1024).  Read at every call, not at
+ *                     sa_initialize_processor; no result depends on it
  * Launch geometry (defaults are the measured optima, tools/sweep_*.sh)
  *   fin_batch, bufs_per_wave, long_cap, long_blocks, max_waves, packed_waves, l2_blocks, ctx_waves, ctx_threads,
  *   chain_sort_threads, chain_sort_blocks, chain_group_max (candidates a chain workgroup sorts in LDS at a time), chain_bucket_target
@@ -547,6 +549,79 @@ _Static_assert(sizeof(sa_gapped_greedy_stats) == 128, "sa_gapped_greedy_stats is
 size_t sa_gapped_align_greedy(const sa_segment_pair* hsps, size_t n, int rev, uint32_t buffer, const sa_gapped_params* p,
                               sa_gapped_alignment** out, sa_gapped_path** paths, uint32_t** ops, size_t* n_ops,
                               sa_gapped_greedy_stats* stats);
+
+/* ---- chaining HSPs into best collinear chains (additive; restated by tests/hsp_chain_model.py) ----------
+ *
+ * sa_chain_hsps reduces a set of HSPs to the highest-scoring collinear chain of every group, in the spirit of LASTZ's
+ * --chain=diag,anti (not claimed to equal it).  It reads no sequence and no table: it needs sa_initialize_interface only.
+ *   Input: n <= 1 << 22 HSPs (len = bases - 1).  With rs = ref_start, qs = query_start: re = rs + len + 1, qe = qs + len + 1, both
+ *     64-bit.  group[n] (NULL: every HSP in group 0) names the set an HSP chains within.
+ *   Predecessor: j < i ("j may precede i") iff group[j] == group[i], re_j <= rs_i and qe_j <= qs_i (abutting is allowed, one base of
+ *     overlap in either sequence is not) and, with max_gap != 0, rs_i - re_j <= max_gap and qs_i - qe_j <= max_gap.
+ *   Penalty (int64): pen(j, i) = diag_pen * |(rs_i - qs_i) - (rs_j - qs_j)| + anti_pen * ((rs_i + qs_i) - (re_j + qe_j)); the second
+ *     term is >= 0 whenever j < i.
+ *   Recurrence (int64): f(i) = score_i + max(0, max over j < i of (f(j) - pen(j, i))).
+ *     Bound: |score| <= 2^31 and n <= 2^22 keep |f| <= 2^53; both penalty terms are below 2^33 * 2^20 = 2^53, so every intermediate
+ *     stays inside +-2^56.
+ *   Canonical rank: the HSPs ordered by (group, ref_start, query_start, len, input index).  j < i implies rank(j) < rank(i).
+ *   Ties: pred(i) is the j < i with the largest f(j) - pen(j, i) provided that value is > 0 (exactly 0: no predecessor); among equal
+ *     values the lowest rank wins.  The best chain of a group ends at its member with the largest f, among equal values at the lowest
+ *     rank, and is the pred walk from there.
+ *   Output: the best chain of every group that has an HSP and whose chain score is >= min_score, groups ascending, members of a chain
+ *     in rank order; the last member's f is the chain score.  With nodes != NULL also f and pred of every input HSP in input order
+ *     (pred: input index of the predecessor, or -1).
+ * Option chain_tile (64 .. 1024, a power of two; default 256) is the tile the device cuts the ranked HSPs into; it is read at every call
+ * (sa_set_option / SEGALIGN_AMD_CHAIN_TILE take effect at the next call) and no result depends on it.  Out-of-range parameters, a bad
+ * chain_tile and n above the limit end the process with a message and exit code 1, like the other entries.  The call takes a slot from
+ * the engine's pool (from a pool of its own before sa_initialize_processor) and may be issued from many threads, but, like every entry
+ * that takes a slot, never while sa_initialize_processor or sa_shutdown_processor runs: both rebuild the slots.  sa_get_option
+ * ("chain_tile") reports what the last sa_initialize_processor resolved, not what a call read. */
+typedef struct sa_chain_params {
+    int32_t diag_pen;   /* penalty per diagonal step, 0 .. 1 << 20 (default 0) */
+    int32_t anti_pen;   /* penalty per antidiagonal step, 0 .. 1 << 20 (default 0) */
+    uint32_t max_gap;   /* largest gap between consecutive members in either sequence; 0: unlimited */
+    uint32_t pad;
+    int64_t min_score;  /* chains that score less are not returned (default 0) */
+} sa_chain_params;
+
+typedef struct sa_chain_member {
+    uint32_t hsp_index; /* input index */
+    uint32_t group;
+    int64_t f;          /* chain score up to and including this member */
+} sa_chain_member;
+
+typedef struct sa_chain_node {
+    int64_t f;
+    int32_t pred;       /* input index of the predecessor, or -1 */
+    uint32_t pad;
+} sa_chain_node;
+
+typedef struct sa_chain_stats {
+    uint64_t hsps;
+    uint64_t groups;       /* groups that hold an HSP */
+    uint64_t chains;       /* chains returned (score >= min_score) */
+    uint64_t members;      /* members returned */
+    uint64_t pair_evals;   /* (j, i) pairs the cross and resolve kernels evaluate */
+    uint64_t tile_steps;   /* cross workgroups plus resolve launches */
+    double kernel_ms;      /* device time of the rank, cross, resolve and finish kernels */
+} sa_chain_stats;
+#ifdef __cplusplus
+static_assert(sizeof(sa_chain_params) == 24, "sa_chain_params is 24 bytes");
+static_assert(sizeof(sa_chain_member) == 16, "sa_chain_member is 16 bytes");
+static_assert(sizeof(sa_chain_node) == 16, "sa_chain_node is 16 bytes");
+static_assert(sizeof(sa_chain_stats) == 56, "sa_chain_stats is 56 bytes");
+#else
+_Static_assert(sizeof(sa_chain_params) == 24, "sa_chain_params is 24 bytes");
+_Static_assert(sizeof(sa_chain_member) == 16, "sa_chain_member is 16 bytes");
+_Static_assert(sizeof(sa_chain_node) == 16, "sa_chain_node is 16 bytes");
+_Static_assert(sizeof(sa_chain_stats) == 56, "sa_chain_stats is 56 bytes");
+#endif
+
+/* Returns the number of members.  *members and *nodes (n entries; nodes nullable) are malloc-ed and released with sa_free_chain; each
+ * is NULL when it would be empty.  p: NULL takes the defaults.  stats: nullable. */
+size_t sa_chain_hsps(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p, sa_chain_member** members,
+                     sa_chain_node** nodes, sa_chain_stats* stats);
+void sa_free_chain(sa_chain_member* members, sa_chain_node* nodes);
 
 const char* sa_version(void);
 

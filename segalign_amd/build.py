@@ -9,7 +9,7 @@ LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libsegalign_hip.so")
 SOURCES = ["encode.hip", "scan.hip", "table.hip", "seeds.hip", "probe.hip", "extend.hip", "dedup.hip", "coverage.hip",
            "arena.hip", "options.hip", "profile.hip", "pool.hip", "front.hip", "core.hip", "api_setup.hip", "api_calls.hip", "api_rm.hip",
-           "api_introspect.hip", "gapped.hip", "cover.hip", "api_gapped.hip"]
+           "api_introspect.hip", "gapped.hip", "cover.hip", "api_gapped.hip", "hspchain.hip", "api_hspchain.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 
 
@@ -50,6 +50,38 @@ def build_lib(force=False, verbose=False):
     return LIB_PATH
 
 
+def kernel_resources(src="hspchain.hip"):
+    """{kernel: {"vgprs", "agprs", "sgprs", "scratch", "lds", "occupancy"}} of a unit's kernels, from the compiler's own resource-usage
+    remarks (device code only, nothing is written).  `python -m segalign_amd.build --resources` prints hspchain.hip's."""
+    import re
+    hipcc = os.environ.get("HIPCC", "hipcc")
+    cmd = [hipcc] + FLAGS + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, src), "-o", os.devnull]
+    out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, check=True).stdout.decode(errors="replace")
+    fields = {"VGPRs": "vgprs", "AGPRs": "agprs", "TotalSGPRs": "sgprs", "ScratchSize [bytes/lane]": "scratch", "LDS Size [bytes/block]": "lds",
+              "Occupancy [waves/SIMD]": "occupancy"}
+    res, cur = {}, None
+    for line in out.splitlines():
+        m = re.search(r"remark: .*Function Name: (\S+)", line)
+        if m:
+            try:
+                name = subprocess.run(["c++filt", m.group(1)], stdout=subprocess.PIPE, check=True).stdout.decode().strip()
+            except (OSError, subprocess.CalledProcessError) as e:
+                raise RuntimeError("kernel_resources: c++filt is needed to read the kernels' names (%s)" % e)
+            name = re.sub(r"^.*::", "", re.sub(r"\(.*$", "", name.replace("(anonymous namespace)::", "")))
+            cur = res.setdefault(name, {})
+            continue
+        m = re.search(r"remark: .*?\s+([A-Za-z][A-Za-z \[\]/]*): (\d+)", line)
+        if m and cur is not None and m.group(1) in fields:
+            cur[fields[m.group(1)]] = int(m.group(2))
+    if not res:
+        raise RuntimeError("kernel_resources: no resource-usage remark in the compiler's output for %s" % src)
+    for name, r in res.items():
+        missing = sorted(set(fields.values()) - set(r))
+        if missing:
+            raise RuntimeError("kernel_resources: %s: no %s in the compiler's remarks" % (name, ", ".join(missing)))
+    return res
+
+
 HOST_SRC = os.path.join(HERE, "host", "segalign_host.cpp")
 HOST_BIN = os.path.join(HERE, "bin", "segalign_host")
 RM_HOST_SRC = os.path.join(HERE, "host", "segalign_rm_host.cpp")
@@ -71,5 +103,9 @@ def build_host(force=False):
 
 
 if __name__ == "__main__":
+    if "--resources" in sys.argv:
+        for k, v in sorted(kernel_resources().items()):
+            print("%-32s %s" % (k, " ".join("%s=%d" % kv for kv in sorted(v.items()))))
+        sys.exit(0)
     print(build_lib(force="--force" in sys.argv, verbose=True))
     print(build_host(force="--force" in sys.argv))

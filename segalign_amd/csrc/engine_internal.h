@@ -12,6 +12,7 @@
 //   api_calls.hip      SeedAndFilter and its additive forms (range, chunks, interval, call lists), ExtendHits, DeviceMakeSeeds
 //   api_rm.hip         repeat-masker entries and the device-side coverage post-processing
 //   api_gapped.hip     sa_gapped_extend / _align / _align_greedy: gapped extension of HSP anchors, paths, cover (gapped.hip, cover.hip)
+//   api_hspchain.hip   sa_chain_hsps: the best collinear chain of every group of HSPs (hspchain.hip)
 //   api_introspect.hip statistics, lookup mode, copies of device state for the tests
 #pragma once
 #include <hip/hip_runtime.h>
@@ -336,6 +337,10 @@ struct Slot {
     DevBuf<uint64_t> cover_key[2], cover_run[2];
     DevBuf<uint8_t> cover_segs, cover_work, cover_temp;
     DevBuf<uint32_t> cover_edges;
+    // sa_chain_hsps (api_hspchain.hip, hspchain.hip): the ranked HSPs with f and pred, sort keys and finish arrays, the cross launches'
+    // partial bests, rocPRIM's temporary storage
+    DevBuf<uint8_t> hspchain_work, hspchain_partial, hspchain_temp;
+    bool early = false;               // taken from the pool that serves sa_chain_hsps before InitializeProcessor (pool.hip)
 };
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -473,6 +478,7 @@ extern thread_local std::vector<uint2> t_audit;
 extern thread_local uint32_t t_front_flags;  // SA_PATH_* bits the front of the calling thread's current call has set (front.hip -> core.hip)
 
 int64_t opt_value(const char* name);  // the option table (options.hip)
+int64_t opt_value_now(const char* name);  // ... for an option read at call time: sa_set_option > environment > default as of now, unclamped
 void resolve_options();
 void require_init(const char* who);
 void require_proc(const char* who, uint32_t buffer);
@@ -515,6 +521,8 @@ void prof_flush(Slot* sl);  // call after the slot's stream has been synchronise
 // ---- slots, token pool, worker pool (pool.hip) ----
 Slot* acquire_slot();
 void release_slot(Slot* s);
+Slot* acquire_slot_early();  // for an entry that needs InitializeInterface only: acquire_slot() once the processor is initialised,
+                             // before that a slot of device 0 set up on demand (give it back with release_slot too)
 void slot_init(Slot& s, DevCtx* dc);
 void slot_destroy(Slot& s);
 void run_parallel(size_t n, int threads, std::function<void(size_t)> fn);

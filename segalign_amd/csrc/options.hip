@@ -137,6 +137,7 @@ static Option g_opts[] = {
     {"gapped_greedy_batch", 1024, 1, 1 << 20, 0},      // anchors per priority batch of sa_gapped_align_greedy (swept); results do not depend on it
     {"gapped_greedy_edges", 1 << 26, 1, 1ll << 32, 0}, // in-edges one resolve pass of sa_gapped_align_greedy holds (4 bytes each); a batch with more is resolved in several passes, with the same result
     {"gapped_pieces", 1, 1, 1024, 0},                  // pieces a side of the gapped entries may take: a side that ends at max_extent is continued from its best cell; 1: never
+    {"chain_tile", 256, 64, 1024, 0},                  // HSPs per tile of sa_chain_hsps (a power of two); read at every call (opt_value_now), results do not depend on it
     // launch geometry (swept by tools/sweep_*.sh; the defaults are the measured optima)
     {"fin_batch", 48, 1, 64, 0}, {"bufs_per_wave", 8, 1, 1 << 20, 0}, {"long_cap", 128, 0, 2 * PACK_PAD, 0},
     {"long_blocks", 1792, 1, 1 << 20, 0}, {"max_waves", 4096, 4, 1 << 20, 0}, {"packed_waves", 4096, 8, 1 << 20, 0},
@@ -160,21 +161,28 @@ int64_t opt_value(const char* name) {
     Option* o = find_option(name);
     return o ? o->value : 0;
 }
-void resolve_options() {
-    for (auto& o : g_opts) {
-        int64_t v = o.def;
-        char env[96] = "SEGALIGN_AMD_";
-        size_t n = strlen(env);
-        for (const char* c = o.name; *c && n + 1 < sizeof(env); c++) env[n++] = (char)toupper((unsigned char)*c);
-        env[n] = '\0';
-        if (o.api_set) v = o.api_value;
-        else if (const char* e = getenv(env)) {
-            char* endp = nullptr;
-            v = strtoll(e, &endp, 10);
-            if (endp == e) v = 1;  // a switch set to a non-number ("yes") counts as on
-        }
-        o.value = std::max(o.lo, std::min(o.hi, v));
+static int64_t requested(const Option& o) {  // sa_set_option > environment > default, not yet clamped
+    int64_t v = o.def;
+    char env[96] = "SEGALIGN_AMD_";
+    size_t n = strlen(env);
+    for (const char* c = o.name; *c && n + 1 < sizeof(env); c++) env[n++] = (char)toupper((unsigned char)*c);
+    env[n] = '\0';
+    if (o.api_set) v = o.api_value;
+    else if (const char* e = getenv(env)) {
+        char* endp = nullptr;
+        v = strtoll(e, &endp, 10);
+        if (endp == e) v = 1;  // a switch set to a non-number ("yes") counts as on
     }
+    return v;
+}
+// An option an entry reads at call time (chain_tile): the requested value as it stands now, unclamped -- the entry checks it.  Nothing is
+// stored: sa_get_option goes on reporting what the last InitializeProcessor resolved.
+int64_t opt_value_now(const char* name) {
+    const Option* o = find_option(name);
+    return o ? requested(*o) : 0;
+}
+void resolve_options() {
+    for (auto& o : g_opts) o.value = std::max(o.lo, std::min(o.hi, requested(o)));
     SLOTS_PER_DEVICE = (int)opt_value("slots");
     g_chunks_per_call = (int)opt_value("chunks_per_call");
     g_call_hits = opt_value("call_hits");

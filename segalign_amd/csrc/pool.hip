@@ -18,7 +18,42 @@ Slot* acquire_slot() {  // src/seed_filter.cu:699-708
     check_set_device(g_dev[t.first]->dev, "SeedAndFilter");
     return &g_dev[t.first]->slots[t.second];
 }
+// Before InitializeProcessor the token pool is empty and no slot exists.  An entry that needs neither sequences nor tables
+// (sa_chain_hsps) is served from the first slots of device 0 then, set up on first use and counted out by g_early_tokens;
+// InitializeProcessor finds them initialised and keeps them, ShutdownProcessor destroys them like any slot.
+static bool g_early_filled = false;  // (guarded by g_mu)
+static std::vector<int> g_early_tokens;
+Slot* acquire_slot_early() {
+    std::unique_lock<std::mutex> lk(g_mu);
+    if (g_proc_init) {
+        lk.unlock();
+        return acquire_slot();
+    }
+    if (!g_early_filled) {
+        g_early_filled = true;
+        for (int k = 3; k >= 0; k--) g_early_tokens.push_back(k);
+    }
+    g_cv.wait(lk, [] { return !g_early_tokens.empty(); });
+    const int k = g_early_tokens.back();
+    g_early_tokens.pop_back();
+    DevCtx* dc = g_dev[0];
+    check_set_device(dc->dev, "early slot");
+    Slot& s = dc->slots[k];
+    if (!s.stream) slot_init(s, dc);
+    s.early = true;
+    return &s;
+}
 void release_slot(Slot* s) {  // src/seed_filter.cu:798-803
+    if (s->early) {
+        int k = (int)(s - s->ctx->slots);
+        {
+            std::lock_guard<std::mutex> lk(g_mu);
+            s->early = false;
+            g_early_tokens.push_back(k);
+        }
+        g_cv.notify_all();
+        return;
+    }
     int di = -1, si = -1;
     for (int d = 0; d < g_ndev; d++)
         for (int k = 0; k < SLOTS_PER_DEVICE; k++)
@@ -92,6 +127,9 @@ void slot_destroy(Slot& s) {
     s.cover_work.release("cover work");
     s.cover_temp.release("cover temp");
     s.cover_edges.release("cover edges");
+    s.hspchain_work.release("hsp chain");
+    s.hspchain_partial.release("hsp chain partials");
+    s.hspchain_temp.release("hsp chain temp");
     s.cand_list.release("candidate list");
     s.l2_list.release("second-level list");
     s.audit.release("audit list");

@@ -39,6 +39,7 @@ C_ABI_SYMBOLS = [
     "sa_get_lookup_mode", "sa_get_neighbourhood_entries",
     "sa_seed_calls", "sa_count_call_hits", "sa_count_chunk_hits", "sa_get_wga_chunk", "sa_release_arena", "sa_set_option", "sa_reset_option", "sa_get_option", "sa_option_count", "sa_option_name", "sa_get_audit",
     "sa_gapped_extend", "sa_free_gapped", "sa_gapped_align", "sa_free_gapped_align", "sa_gapped_align_greedy",
+    "sa_chain_hsps", "sa_free_chain",
 ]
 IVL_DTYPE = np.dtype([("query_start", "<u4"), ("len", "<u4")])  # struct Segment, repeat_masker_src/graph.h:32-35
 STRAND_PLUS, STRAND_MINUS, STRAND_BOTH = 1, 2, 3
@@ -73,6 +74,19 @@ class GappedAlignStats(C.Structure):
 class GappedGreedyStats(C.Structure):
     _fields_ = [("align", GappedAlignStats), ("covered", C.c_uint64), ("below_thresh", C.c_uint64), ("skipped", C.c_uint64),
                 ("priority_batches", C.c_uint64), ("cover_segments", C.c_uint64), ("cover_ms", C.c_double)]
+
+
+CHAIN_MEMBER_DTYPE = np.dtype([("hsp_index", "<u4"), ("group", "<u4"), ("f", "<i8")])  # sa_chain_member
+CHAIN_NODE_DTYPE = np.dtype([("f", "<i8"), ("pred", "<i4"), ("pad", "<u4")])  # sa_chain_node
+
+
+class ChainParams(C.Structure):
+    _fields_ = [("diag_pen", C.c_int32), ("anti_pen", C.c_int32), ("max_gap", C.c_uint32), ("pad", C.c_uint32), ("min_score", C.c_int64)]
+
+
+class ChainStats(C.Structure):
+    _fields_ = [("hsps", C.c_uint64), ("groups", C.c_uint64), ("chains", C.c_uint64), ("members", C.c_uint64), ("pair_evals", C.c_uint64),
+                ("tile_steps", C.c_uint64), ("kernel_ms", C.c_double)]
 
 
 class CallStats(C.Structure):
@@ -178,6 +192,10 @@ def lib():
     L.sa_gapped_align_greedy.restype = C.c_size_t
     L.sa_gapped_align_greedy.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(GappedParams), C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(GappedGreedyStats)]
+    L.sa_chain_hsps.restype = C.c_size_t
+    L.sa_chain_hsps.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(ChainParams), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                C.POINTER(ChainStats)]
+    L.sa_free_chain.argtypes = [C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -411,6 +429,28 @@ def GappedAlignGreedy(hsps, rev, buffer, gap_open=400, gap_extend=30, ydrop=9430
     res = _gapped(lib().sa_gapped_align_greedy, lib().sa_free_gapped_align, hsps, rev, buffer,
                   (gap_open, gap_extend, ydrop, gappedthresh, max_extent, max_band), st)
     return (*res, _flat(st))
+
+
+def ChainHsps(hsps, groups=None, diag_pen=0, anti_pen=0, max_gap=0, min_score=0, nodes=False):
+    """The best collinear chain of every group of HSPs (sa_chain_hsps; contract in include/segalign_amd.h).
+    hsps: SEG_DTYPE records; groups: one uint32 per HSP (None: all in group 0).  -> (CHAIN_MEMBER_DTYPE members, stats dict), or with
+    nodes=True (members, CHAIN_NODE_DTYPE nodes in input order, stats dict).  Needs InitializeInterface only."""
+    h = np.ascontiguousarray(hsps, dtype=SEG_DTYPE)
+    g = None if groups is None else np.ascontiguousarray(groups, dtype=np.uint32)
+    if g is not None and g.shape != h.shape:
+        raise ValueError("groups: one entry per HSP")
+    p = ChainParams(int(diag_pen), int(anti_pen), int(max_gap), 0, int(min_score))
+    mem, nod, st = C.c_void_p(), C.c_void_p(), ChainStats()
+    m = lib().sa_chain_hsps(h.ctypes.data if h.size else None, h.size, g.ctypes.data if g is not None and g.size else None, C.byref(p),
+                            C.byref(mem), C.byref(nod) if nodes else None, C.byref(st))
+
+    def take(ptr, count, dtype):
+        if not count or not ptr.value:
+            return np.zeros(0, dtype=dtype)
+        return np.frombuffer((C.c_char * (count * dtype.itemsize)).from_address(ptr.value), dtype=dtype).copy()
+    res_m, res_n = take(mem, m, CHAIN_MEMBER_DTYPE), take(nod, h.size, CHAIN_NODE_DTYPE)
+    lib().sa_free_chain(mem, nod)
+    return (res_m, res_n, _flat(st)) if nodes else (res_m, _flat(st))
 
 
 def cigar(ops):

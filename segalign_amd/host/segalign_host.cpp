@@ -43,6 +43,9 @@ struct Config {  // src/graph.h:32-76 with the defaults of src/main.cpp:61-124
     int gpu_pieces = 0;       // --gpu_pieces=N (with --gpu_gapped): engine option gapped_pieces, set before sa_initialize_processor; 0: left alone
     uint32_t gpu_max_extent = 0;  // --gpu_max_extent=N (with --gpu_gapped): sa_gapped_params.max_extent; 0: the engine's default
     bool gpu_skip_covered = false;  // --gpu_skip_covered (with --gpu_gapped): the files hold sa_gapped_align_greedy's alignments
+    bool gpu_chain = false;   // --gpu_chain[=diag,anti]: a .chain file next to every .segments file (sa_chain_hsps); the gapped entries get its HSPs only
+    int chain_diag = 0, chain_anti = 0;  // sa_chain_params.diag_pen / anti_pen
+    uint32_t chain_gap = 0;   // --gpu_chain_gap=N: sa_chain_params.max_gap; 0: unlimited
     int gap_open = 400, gap_extend = 30;
     int xdrop = 910, hspthresh = 3000, ydrop = 9430, gappedthresh = -1;
     uint32_t wga_chunk = 250000, lastz_interval = 10000000, seq_block_size = 500000000;
@@ -236,6 +239,36 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
         if (!rev) for (size_t i = 0; i < v.size(); i++) emit(v[i]);
         else for (size_t i = v.size(); i-- > 0;) emit(v[i]);  // :130: reverse vector order on the minus strand
         fclose(f);
+        std::vector<sa_segment_pair> kept;  // with --gpu_chain: the chains' HSPs in their order within v
+        if (cfg.gpu_chain) {  // the best collinear chain of every (target record, query record) pair of this file, DESIGN.md 15
+            if (v.size() > ((size_t)1 << 22))  // sa_chain_hsps' limit, told in the host's words
+            {
+                fprintf(stderr, "--gpu_chain: %s holds %zu HSPs, more than the 4194304 one chaining call takes; lower --lastz_interval\n", seg_name.c_str(), v.size());
+                exit(8);
+            }
+            std::vector<uint64_t> rec_pair(v.size());
+            for (size_t i = 0; i < v.size(); i++)
+                rec_pair[i] = (uint64_t)chr_of(R.chr_start, v[i].ref_start + r_block_start) << 32 | (uint64_t)chr_of(qs, v[i].query_start + q_block_start);
+            std::vector<uint64_t> pairs(rec_pair);  // group = rank of the pair among the file's pairs: ascending (target record, query record)
+            std::sort(pairs.begin(), pairs.end());
+            pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+            std::vector<uint32_t> group(v.size());
+            for (size_t i = 0; i < v.size(); i++) group[i] = (uint32_t)(std::lower_bound(pairs.begin(), pairs.end(), rec_pair[i]) - pairs.begin());
+            sa_chain_params cp = {cfg.chain_diag, cfg.chain_anti, cfg.chain_gap, 0, 0};
+            sa_chain_member* mem = nullptr;
+            const size_t nm = sa_chain_hsps(v.data(), v.size(), group.data(), &cp, &mem, nullptr, nullptr);
+            std::string cname = base + ".chain";
+            f = fopen((cfg.outdir + "/" + cname).c_str(), "w");
+            if (!f) die(7, "cant open file: %s", cname.c_str());
+            std::vector<uint32_t> idx(nm);
+            for (size_t k = 0; k < nm; k++) { emit(v[mem[k].hsp_index]); idx[k] = mem[k].hsp_index; }  // the order sa_chain_hsps returns, on both strands
+            fclose(f);
+            sa_free_chain(mem, nullptr);
+            std::sort(idx.begin(), idx.end());  // an HSP is a member of one chain at most: no duplicates
+            kept.reserve(nm);
+            for (uint32_t i : idx) kept.push_back(v[i]);
+        }
+        const std::vector<sa_segment_pair>& anchors = cfg.gpu_chain ? kept : v;  // what the gapped entries extend
         if (cfg.gpu_gapped) {  // the gapped extension of the same HSPs on the device: [start, end) extents printed like the segments
             sa_gapped_params gp = {cfg.gap_open, cfg.gap_extend, cfg.ydrop, cfg.gappedthresh, cfg.gpu_max_extent, 0};
             sa_gapped_alignment* al = nullptr;
@@ -243,9 +276,9 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
             uint32_t* ops = nullptr;
             size_t n_ops = 0;
             const bool with_paths = cfg.gpu_maf || cfg.gpu_skip_covered;
-            const size_t na = cfg.gpu_skip_covered ? sa_gapped_align_greedy(v.data(), v.size(), rev, buffer, &gp, &al, &paths, &ops, &n_ops, nullptr)
-                              : cfg.gpu_maf        ? sa_gapped_align(v.data(), v.size(), rev, buffer, &gp, 0, &al, &paths, &ops, &n_ops, nullptr)
-                                                   : sa_gapped_extend(v.data(), v.size(), rev, buffer, &gp, 0, &al, nullptr);
+            const size_t na = cfg.gpu_skip_covered ? sa_gapped_align_greedy(anchors.data(), anchors.size(), rev, buffer, &gp, &al, &paths, &ops, &n_ops, nullptr)
+                              : cfg.gpu_maf        ? sa_gapped_align(anchors.data(), anchors.size(), rev, buffer, &gp, 0, &al, &paths, &ops, &n_ops, nullptr)
+                                                   : sa_gapped_extend(anchors.data(), anchors.size(), rev, buffer, &gp, 0, &al, nullptr);
             std::string gname = base + ".gapped";
             FILE* g = fopen((cfg.outdir + "/" + gname).c_str(), "w");
             if (!g) die(7, "cant open file: %s", gname.c_str());
@@ -320,7 +353,11 @@ static void usage() {
             "  --gpu_maf (with --gpu_gapped: the alignments of each .gapped file as a .maf file in LASTZ's maf- layout)\n"
             "  --gpu_skip_covered (with --gpu_gapped: extend anchors best first and skip those on earlier alignments)\n"
             "  --gpu_max_extent=N (with --gpu_gapped: bases one piece of an alignment side may span; default 65536)\n"
-            "  --gpu_pieces=N (with --gpu_gapped: continue an alignment side that ends at the extent cap, up to N pieces; default 1)\n");
+            "  --gpu_pieces=N (with --gpu_gapped: continue an alignment side that ends at the extent cap, up to N pieces; default 1)\n"
+            "  --gpu_chain[=diag,anti] (a .chain file next to each .segments file: the best collinear chain of every target record x query\n"
+            "      record pair, with penalties per diagonal and antidiagonal step, default 0,0; --gpu_gapped then extends the chains' HSPs only)\n"
+            "  --gpu_chain_gap=N (with --gpu_chain: largest gap between consecutive chain members in either sequence; default 0, unlimited)\n"
+            "      a .segments file may hold at most 4194304 HSPs with --gpu_chain\n");
 }
 
 int main(int argc, char** argv) {
@@ -360,6 +397,19 @@ int main(int argc, char** argv) {
         else if (opt(a, "--gpu_pieces", v)) {
             cfg.gpu_pieces = atoi(v.c_str());
             if (cfg.gpu_pieces < 1 || cfg.gpu_pieces > 1024) { fprintf(stderr, "bad --gpu_pieces=%s (1 .. 1024)\n", v.c_str()); return 1; }
+        }
+        else if (!strcmp(a, "--gpu_chain")) cfg.gpu_chain = true;
+        else if (opt(a, "--gpu_chain", v)) {
+            cfg.gpu_chain = true;
+            char tail;
+            if (sscanf(v.c_str(), "%d,%d%c", &cfg.chain_diag, &cfg.chain_anti, &tail) != 2 || cfg.chain_diag < 0 || cfg.chain_diag > (1 << 20) ||
+                cfg.chain_anti < 0 || cfg.chain_anti > (1 << 20)) { fprintf(stderr, "bad --gpu_chain=%s (diag,anti; each 0 .. %d)\n", v.c_str(), 1 << 20); return 1; }
+        }
+        else if (opt(a, "--gpu_chain_gap", v)) {
+            char* endp = nullptr;
+            const long long gap = strtoll(v.c_str(), &endp, 10);
+            if (endp == v.c_str() || *endp || gap < 0 || gap > 0xffffffffll) { fprintf(stderr, "bad --gpu_chain_gap=%s (0 .. 4294967295; 0: unlimited)\n", v.c_str()); return 1; }
+            cfg.chain_gap = (uint32_t)gap;
         }
         else if (opt(a, "--gap", v)) {
             if (sscanf(v.c_str(), "%d,%d", &cfg.gap_open, &cfg.gap_extend) != 2) { fprintf(stderr, "bad --gap=%s\n", v.c_str()); return 1; }

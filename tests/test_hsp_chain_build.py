@@ -1,0 +1,14 @@
+"""CPU: the chaining kernels (segalign_amd/csrc/hspchain.hip) as the compiler reports them: every kernel is there and none
+spills to scratch memory."""
+from segalign_amd.build import kernel_resources
+
+KERNELS = ["hspchain_cross_kernel", "hspchain_resolve_kernel", "hspchain_key_minor_kernel", "hspchain_key_major_kernel",
+           "hspchain_gather_kernel", "hspchain_first_kernel", "hspchain_group_starts_kernel", "hspchain_ends_kernel",
+           "hspchain_members_kernel", "hspchain_nodes_kernel"]
+
+
+def test_chain_kernels_use_no_scratch():
+    res = kernel_resources("hspchain.hip")
+    assert sorted(res) == sorted(KERNELS)
+    for k, r in res.items():
+        assert r["scratch"] == 0 and 0 < r["vgprs"] <= 128, (k, r)  # 128: what a workgroup of 1024 threads leaves a lane

@@ -9,8 +9,13 @@ With --pieces N the engine runs with option gapped_pieces = N (sides that end at
 --max-extent M the three entries get max_extent = M; the line then adds the sides continued, their further pieces and the rounds, the
 records still extent-capped or continued and the summed alignment length of each entry.
 
+With --chain [--chain-pen D,A] the HSPs (one group) first go through sa_chain_hsps: the line then adds n, groups, the
+members kept, pair evaluations, tile steps, the chain kernel ms and pair evaluations per second, and the extension (with --align /
+--greedy also the alignment / greedy) times on the chain's members beside those on all HSPs.  f and pred of every HSP and the members
+are checked against the numpy model (tests/hsp_chain_model.py) once per run.
+
   python tools/gapped_bench.py [--workloads standin,lumpy] [--repeat 3] [--align] [--greedy] [--batches 1024,2048,...]
-                               [--pieces N] [--max-extent M]
+                               [--pieces N] [--max-extent M] [--chain] [--chain-pen D,A]
 """
 import argparse
 import functools
@@ -134,7 +139,42 @@ def greedy_fields(hsps, repeat, with_sel=True):
             "trace_mb": int(E.get_option("gapped_trace_mb")), "greedy_ops": int(gops.size)}
 
 
-def run(name, repeat, align=False, greedy=False, with_sel=True, pieces=0):
+def chain_fields(hsps, repeat, pen, align, greedy):
+    """sa_chain_hsps on the HSPs as one group, checked against the numpy model, and the gapped entries on the chain's members."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import hsp_chain_model as M
+    best = None
+    for _ in range(repeat):
+        t0 = time.perf_counter()
+        r = E.ChainHsps(hsps, None, diag_pen=pen[0], anti_pen=pen[1], nodes=True)
+        wall = (time.perf_counter() - t0) * 1e3
+        if best is None or r[2]["kernel_ms"] < best[0][2]["kernel_ms"]:
+            best = (r, wall)
+    (members, nodes, st), wall = best
+    t0 = time.perf_counter()
+    f, pred, want = M.chain(hsps, None, diag_pen=pen[0], anti_pen=pen[1])
+    model_s = time.perf_counter() - t0
+    if not (np.array_equal(nodes["f"], f) and np.array_equal(nodes["pred"], pred) and np.array_equal(members, want)):
+        raise SystemExit("sa_chain_hsps differs from the numpy model")
+    kept = hsps[np.sort(members["hsp_index"])]
+    out = {"chain_pen": list(pen), "chain_n": int(st["hsps"]), "chain_groups": int(st["groups"]), "chain_members": int(st["members"]),
+           "chain_score": int(members["f"][-1]) if members.size else None, "chain_pair_evals": int(st["pair_evals"]),
+           "chain_tile_steps": int(st["tile_steps"]), "chain_tile": int(E.get_option("chain_tile")), "chain_kernel_ms": round(st["kernel_ms"], 3),
+           "chain_call_ms": round(wall, 3), "chain_gpairs_per_s": round(st["pair_evals"] / (st["kernel_ms"] * 1e-3) / 1e9, 3) if st["kernel_ms"] > 0 else None,
+           "chain_model_checked": True, "chain_model_s": round(model_s, 1)}
+    kst = min((E.GappedExtend(kept, False, 0, **KW)[1] for _ in range(repeat)), key=lambda x: x["kernel_ms"])
+    out.update({"kept_extend_ms": round(kst["kernel_ms"], 3), "kept_cells": int(kst["cells"]), "kept_alignments": int(kst["returned"])})
+    if align:
+        ast = min((E.GappedAlign(kept, False, 0, **KW)[3] for _ in range(repeat)), key=lambda x: x["kernel_ms"] + x["trace_ms"] + x["walk_ms"])
+        out["kept_align_kernel_ms"] = round(ast["kernel_ms"] + ast["trace_ms"] + ast["walk_ms"], 3)
+    if greedy:
+        gst = min((E.GappedAlignGreedy(kept, False, 0, **KW)[3] for _ in range(repeat)),
+                  key=lambda x: x["kernel_ms"] + x["trace_ms"] + x["walk_ms"] + x["cover_ms"])
+        out["kept_greedy_kernel_ms"] = round(gst["kernel_ms"] + gst["trace_ms"] + gst["walk_ms"] + gst["cover_ms"], 3)
+    return out
+
+
+def run(name, repeat, align=False, greedy=False, with_sel=True, pieces=0, chain=None):
     t, q = workload(name)
     if greedy or pieces:
         E.set_option("debug", 1)  # sa_gapped_align_greedy then prints its edge count, the continuation its pieces
@@ -181,6 +221,8 @@ def run(name, repeat, align=False, greedy=False, with_sel=True, pieces=0):
                  "trace_bytes": int(ast["trace_bytes"]), "trace_batches": int(ast["trace_batches"]), "ops": int(ops.size)})
     if greedy:
         extra.update(greedy_fields(hsps, repeat, with_sel))
+    if chain is not None:
+        extra.update(chain_fields(hsps, repeat, chain, align, greedy))
     E.ShutdownProcessor()
     if greedy or pieces:
         E.reset_option("debug")
@@ -202,12 +244,15 @@ def main():
     ap.add_argument("--batches", default="", help="with --greedy: one line per gapped_greedy_batch value, greedy only (a sweep)")
     ap.add_argument("--pieces", type=int, default=0, help="engine option gapped_pieces (0: left at its default of 1)")
     ap.add_argument("--max-extent", type=int, default=0, help="max_extent of every entry (0: the default, 65536)")
+    ap.add_argument("--chain", action="store_true", help="also chain the HSPs (sa_chain_hsps) and time the gapped entries on the chain's members")
+    ap.add_argument("--chain-pen", default="0,0", help="with --chain: diag_pen,anti_pen")
     a = ap.parse_args()
+    chain = tuple(int(x) for x in a.chain_pen.split(",")) if a.chain else None
     if a.max_extent:
         KW["max_extent"] = a.max_extent
     for name in a.workloads.split(","):
         if not a.batches:
-            print(json.dumps(run(name, a.repeat, a.align, a.greedy, pieces=a.pieces)), flush=True)
+            print(json.dumps(run(name, a.repeat, a.align, a.greedy, pieces=a.pieces, chain=chain)), flush=True)
             continue
         for b in a.batches.split(","):
             E.set_option("gapped_greedy_batch", int(b))
