@@ -623,6 +623,67 @@ size_t sa_chain_hsps(const sa_segment_pair* hsps, size_t n, const uint32_t* grou
                      sa_chain_node** nodes, sa_chain_stats* stats);
 void sa_free_chain(sa_chain_member* members, sa_chain_node* nodes);
 
+/* ---- peeling HSPs into all collinear chains of a group (additive; restated by tests/hsp_chain_all_model.py) ----------
+ *
+ * sa_chain_hsps_all partitions the HSPs into chains, in the spirit of UCSC's axtChain (not claimed to equal it): the DP runs once,
+ * then chains are peeled off its pred forest best first.
+ *   Input: as for sa_chain_hsps.  The predecessor relation, penalty, recurrence, rank, ties, f and pred are those of sa_chain_hsps, bit
+ *     for bit: both entries run the same code for them.
+ *   Priority: u comes before v iff f(u) > f(v), or f(u) == f(v) and rank(u) < rank(v).  A total order.
+ *   Peeling: used = {}.  For u in priority order: skip u if it is used; otherwise walk v = u, pred(u), pred(pred(u)), ... while v exists
+ *     and is not used, and mark each such v used, with head(v) = u.  The walked nodes are chain(u).  If the walk stopped at a used node
+ *     s, the chain is joined at s and score(u) = f(u) - f(s); otherwise score(u) = f(u).
+ *   Consequences: every HSP belongs to exactly one chain, so the chains partition the input.  The partition does not depend on
+ *     min_score.  The first chain peeled in a group is sa_chain_hsps's chain of that group, with the same score.  A joined chain's
+ *     score includes the penalty of the link it was cut at, as in axtChain; it may be <= 0 when scores are negative.
+ *   Equivalent rule (what the device computes): head(v) is the node of highest priority among v and every node whose pred walk
+ *     reaches v.
+ *   Output: the chains with score >= min_score ordered by (group ascending, score descending, rank of the head ascending), and their
+ *     members grouped by chain in that order, members of a chain in rank order.  On request f and pred of every HSP (as sa_chain_hsps)
+ *     and chain_of[n] in input order: the chain index, or 0xFFFFFFFF for a member of a chain dropped by min_score.
+ * Validation, exit behaviour, slots, thread safety and option chain_tile are those of sa_chain_hsps. */
+typedef struct sa_chain_record {
+    uint32_t group;
+    uint32_t head;          /* input index of the chain's head: its member of highest priority, the last in rank order */
+    uint32_t first_member;  /* index of its first member in the member array */
+    uint32_t n_members;
+    int64_t score;
+    int32_t joined;         /* input index of the node the chain was cut at, or -1 */
+    uint32_t pad;
+} sa_chain_record;
+
+typedef struct sa_chain_all_member {
+    uint32_t hsp_index; /* input index */
+    uint32_t group;
+    uint32_t chain;     /* index into the chain array */
+    uint32_t pad;
+    int64_t f;          /* the DP value of this member */
+} sa_chain_all_member;
+
+typedef struct sa_chain_all_stats {
+    sa_chain_stats chain;  /* as sa_chain_hsps; chains and members count what is returned; kernel_ms: the rank and DP kernels */
+    uint64_t chains_all;   /* chains before min_score */
+    uint64_t joined;       /* returned chains that are joined */
+    uint64_t peel_rounds;  /* pointer-doubling rounds: max(1, ceil(log2 n)) */
+    double peel_ms;        /* device time of everything after the DP */
+} sa_chain_all_stats;
+#ifdef __cplusplus
+static_assert(sizeof(sa_chain_record) == 32, "sa_chain_record is 32 bytes");
+static_assert(sizeof(sa_chain_all_member) == 24, "sa_chain_all_member is 24 bytes");
+static_assert(sizeof(sa_chain_all_stats) == 88, "sa_chain_all_stats is 88 bytes");
+#else
+_Static_assert(sizeof(sa_chain_record) == 32, "sa_chain_record is 32 bytes");
+_Static_assert(sizeof(sa_chain_all_member) == 24, "sa_chain_all_member is 24 bytes");
+_Static_assert(sizeof(sa_chain_all_stats) == 88, "sa_chain_all_stats is 88 bytes");
+#endif
+
+/* Returns the number of members.  *chains (*n_chains entries), *members, *nodes and *chain_of (n entries each; both nullable) are
+ * malloc-ed and released with sa_free_chain_all; each is NULL when it would be empty.  p: NULL takes the defaults.  stats: nullable. */
+size_t sa_chain_hsps_all(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p, sa_chain_record** chains,
+                         size_t* n_chains, sa_chain_all_member** members, sa_chain_node** nodes, uint32_t** chain_of,
+                         sa_chain_all_stats* stats);
+void sa_free_chain_all(sa_chain_record* chains, sa_chain_all_member* members, sa_chain_node* nodes, uint32_t* chain_of);
+
 const char* sa_version(void);
 
 #ifdef __cplusplus

@@ -9,7 +9,7 @@ LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libsegalign_hip.so")
 SOURCES = ["encode.hip", "scan.hip", "table.hip", "seeds.hip", "probe.hip", "extend.hip", "dedup.hip", "coverage.hip",
            "arena.hip", "options.hip", "profile.hip", "pool.hip", "front.hip", "core.hip", "api_setup.hip", "api_calls.hip", "api_rm.hip",
-           "api_introspect.hip", "gapped.hip", "cover.hip", "api_gapped.hip", "hspchain.hip", "api_hspchain.hip"]
+           "api_introspect.hip", "gapped.hip", "cover.hip", "api_gapped.hip", "hspchain.hip", "hsppeel.hip", "api_hspchain.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 
 
@@ -52,7 +52,7 @@ def build_lib(force=False, verbose=False):
 
 def kernel_resources(src="hspchain.hip"):
     """{kernel: {"vgprs", "agprs", "sgprs", "scratch", "lds", "occupancy"}} of a unit's kernels, from the compiler's own resource-usage
-    remarks (device code only, nothing is written).  `python -m segalign_amd.build --resources` prints hspchain.hip's."""
+    remarks (device code only, nothing is written).  `python -m segalign_amd.build --resources [unit.hip]` prints them (hspchain.hip's by default)."""
     import re
     hipcc = os.environ.get("HIPCC", "hipcc")
     cmd = [hipcc] + FLAGS + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, src), "-o", os.devnull]
@@ -103,8 +103,10 @@ def build_host(force=False):
 
 
 if __name__ == "__main__":
-    if "--resources" in sys.argv:
-        for k, v in sorted(kernel_resources().items()):
+    if "--resources" in sys.argv:  # --resources [unit]: hspchain.hip unless a unit such as hsppeel.hip follows
+        at = sys.argv.index("--resources") + 1
+        unit = sys.argv[at] if at < len(sys.argv) and sys.argv[at].endswith(".hip") else "hspchain.hip"
+        for k, v in sorted(kernel_resources(unit).items()):
             print("%-32s %s" % (k, " ".join("%s=%d" % kv for kv in sorted(v.items()))))
         sys.exit(0)
     print(build_lib(force="--force" in sys.argv, verbose=True))

@@ -1,9 +1,12 @@
-// api_hspchain.hip -- C-ABI sa_chain_hsps: the best collinear chain of every group of HSPs (contract: include/segalign_amd.h).
-// The host side: checks, the slot, rank (two stable radix sorts), the tile loop (hspchain.hip: cross, resolve), finish (group starts, ends,
-// members, nodes) and the counts the kernels' work is reported by.
+// api_hspchain.hip -- C-ABI sa_chain_hsps: the best collinear chain of every group of HSPs (contract: include/segalign_amd.h),
+// and sa_chain_hsps_all: all chains of every group, peeled best first.
+// The host side: checks, the slot, rank (two stable radix sorts) and the tile loop (hspchain.hip: cross, resolve), shared by both; then
+// sa_chain_hsps's finish (group starts, ends, members, nodes) or the peel (hsppeel.hip: subtree minimum, chain order, members), and the
+// counts the kernels' work is reported by.
 #include "engine_internal.h"
 #include "gapped.h"  // cover.hip's rocPRIM wrappers: cover_sort_anchors, cover_scan_offsets
 #include "hspchain.h"
+#include "hsppeel.h"
 
 using namespace sa;
 
@@ -26,19 +29,20 @@ struct Take {  // 256-byte-aligned pieces of one buffer: sized with base == null
 };
 
 struct Events {  // pairs of events on the slot's stream: span k runs from mark(2 k) to mark(2 k + 1)
-    static constexpr int N = 8;
+    static constexpr int MAX = 10;
     hipStream_t s;
-    hipEvent_t e[N];
-    explicit Events(hipStream_t st) : s(st) {
-        for (hipEvent_t& x : e) ok(hipEventCreate(&x));
+    int n;  // events in use: 8 for sa_chain_hsps, 10 for sa_chain_hsps_all
+    hipEvent_t e[MAX];
+    Events(hipStream_t st, int count) : s(st), n(count) {
+        for (int i = 0; i < n; i++) ok(hipEventCreate(&e[i]));
     }
     ~Events() {
-        for (hipEvent_t x : e) hipEventDestroy(x);
+        for (int i = 0; i < n; i++) hipEventDestroy(e[i]);
     }
     void mark(int i) { ok(hipEventRecord(e[i], s)); }
-    double total() {  // after the stream has been synchronised
+    double total(int first, int spans) {  // spans first .. first + spans - 1, after the stream has been synchronised
         double ms = 0;
-        for (int k = 0; k < N; k += 2) {
+        for (int k = 2 * first; k < 2 * (first + spans); k += 2) {
             float x = 0;
             ok(hipEventElapsedTime(&x, e[k], e[k + 1]));
             ms += x;
@@ -50,44 +54,40 @@ struct Events {  // pairs of events on the slot's stream: span k runs from mark(
     }
 };
 
-}  // namespace
-
-extern "C" {
-
-size_t sa_chain_hsps(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p, sa_chain_member** members,
-                     sa_chain_node** nodes, sa_chain_stats* stats) {
-    *members = nullptr;
-    if (nodes) *nodes = nullptr;
-    sa_chain_stats st;
-    memset(&st, 0, sizeof(st));
-    if (stats) *stats = st;
-    require_init("ChainHsps");
+// What the rank step and the DP leave on the slot's stream, for the finish of sa_chain_hsps and the peel of sa_chain_hsps_all.
+struct ChainDp {
+    Slot* sl = nullptr;
+    uint32_t N = 0, G = 0;
     sa_chain_params P = {0, 0, 0, 0, 0};
-    if (p) P = *p;
-    if (P.diag_pen < 0 || P.diag_pen > (1 << 20)) bad("diag_pen", P.diag_pen);
-    if (P.anti_pen < 0 || P.anti_pen > (1 << 20)) bad("anti_pen", P.anti_pen);
-    if (n > HSPCHAIN_MAX_N) bad("the number of HSPs", (long long)n);
-    const int64_t tile_opt = opt_value_now("chain_tile");
-    if (tile_opt < 64 || tile_opt > 1024 || (tile_opt & (tile_opt - 1))) bad("option chain_tile", tile_opt);
-    if (n == 0) return 0;
-    const uint32_t N = (uint32_t)n, T = (uint32_t)tile_opt, tiles = (N + T - 1) / T;
+    HspChainArgs a;
+    const uint32_t* order = nullptr;  // rank -> input index
+    uint32_t *head = nullptr, *gstart = nullptr, *gend = nullptr, *glen = nullptr;  // head[r]: rank r starts a group
+    uint64_t *gidx = nullptr, *goff = nullptr, *key_a = nullptr, *key_b = nullptr;
+    uint32_t *idx_b = nullptr;  // free after the rank step, like key_a and key_b
+    sa_chain_member* d_members = nullptr;
+    sa_chain_node* d_nodes = nullptr;
+    void* temp = nullptr;
+    size_t temp_bytes = 0;
+};
 
-    Slot* sl = acquire_slot_early();
+// The slot's buffers, the upload, rank and the DP (spans 0 and 1 of ev) for n > 0 HSPs on the slot d.sl.  Returns with the stream
+// synchronised, G known and st's pair_evals and tile_steps counted.
+void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, uint32_t T, ChainDp& d, Events& ev, sa_chain_stats& st) {
+    const uint32_t N = (uint32_t)n, tiles = (N + T - 1) / T;
+    d.N = N;
+    Slot* sl = d.sl;
     hipStream_t s = sl->stream;
 
     sa_segment_pair* d_hsps;
-    uint32_t *d_group, *idx_a, *idx_b, *rs, *qs, *ln, *gr, *pred, *head, *first, *gstart, *gend, *glen;
+    uint32_t *d_group, *idx_a, *rs, *qs, *ln, *gr, *pred, *first;
     int32_t* sc;
-    uint64_t *key_a, *key_b, *gidx, *goff;
     int64_t* f;
-    sa_chain_member* d_members;
-    sa_chain_node* d_nodes;
     auto layout = [&](Take& t) {
-        t(d_hsps, N); t(d_group, N); t(key_a, N); t(key_b, N); t(idx_a, N); t(idx_b, N);
+        t(d_hsps, N); t(d_group, N); t(d.key_a, N); t(d.key_b, N); t(idx_a, N); t(d.idx_b, N);
         t(rs, N); t(qs, N); t(ln, N); t(gr, N); t(sc, N); t(f, N); t(pred, N);
-        t(head, (size_t)N + 1); t(gidx, (size_t)N + 1); t(first, tiles);
-        t(gstart, N); t(gend, N); t(glen, (size_t)N + 1); t(goff, (size_t)N + 1);
-        t(d_members, N); t(d_nodes, N);
+        t(d.head, (size_t)N + 1); t(d.gidx, (size_t)N + 1); t(first, tiles);
+        t(d.gstart, N); t(d.gend, N); t(d.glen, (size_t)N + 1); t(d.goff, (size_t)N + 1);
+        t(d.d_members, N); t(d.d_nodes, N);
     };
     {
         Take size{nullptr};
@@ -100,41 +100,40 @@ size_t sa_chain_hsps(const sa_segment_pair* hsps, size_t n, const uint32_t* grou
     sl->hspchain_partial.ensure((size_t)tiles * T * sizeof(HspChainPartial), "hsp chain partials");
     HspChainPartial* partial = (HspChainPartial*)sl->hspchain_partial.p;
     size_t sort_bytes = 0, scan_bytes = 0;
-    cover_sort_anchors(nullptr, &sort_bytes, key_a, key_b, idx_a, idx_b, N, s);
-    cover_scan_offsets(nullptr, &scan_bytes, head, gidx, N, s);
-    size_t temp_bytes = std::max(sort_bytes, scan_bytes);
-    sl->hspchain_temp.ensure(std::max<size_t>(temp_bytes, 256), "hsp chain temp");
-    void* temp = sl->hspchain_temp.p;
+    cover_sort_anchors(nullptr, &sort_bytes, d.key_a, d.key_b, idx_a, d.idx_b, N, s);
+    cover_scan_offsets(nullptr, &scan_bytes, d.head, d.gidx, N, s);
+    d.temp_bytes = std::max(sort_bytes, scan_bytes);
+    sl->hspchain_temp.ensure(std::max<size_t>(d.temp_bytes, 256), "hsp chain temp");
+    void* temp = d.temp = sl->hspchain_temp.p;
 
-    HspChainArgs a;
+    HspChainArgs& a = d.a;
     a.rs = rs; a.qs = qs; a.ln = ln; a.gr = gr; a.sc = sc; a.f = f; a.pred = pred;
     a.n = N;
     a.tile = T;
-    a.diag_pen = P.diag_pen;
-    a.anti_pen = P.anti_pen;
-    a.max_gap = P.max_gap;
+    a.diag_pen = d.P.diag_pen;
+    a.anti_pen = d.P.anti_pen;
+    a.max_gap = d.P.max_gap;
 
     check_memcpy(hipMemcpyAsync(d_hsps, hsps, n * sizeof(sa_segment_pair), hipMemcpyHostToDevice, s), "hsp chain: HSPs");
     if (group) check_memcpy(hipMemcpyAsync(d_group, group, n * sizeof(uint32_t), hipMemcpyHostToDevice, s), "hsp chain: groups");
-    Events ev(s);
 
     // rank: stable sort by (query_start, len) with the input index as value, then by (group, ref_start); idx_a ends up as rank -> input index
     std::vector<uint32_t> h_first(tiles);
     ev.mark(0);
     {
         ProfScope ps(sl, "hspchain_rank");
-        launch_hspchain_key_minor(d_hsps, N, key_a, idx_a, s);
-        cover_sort_anchors(temp, &temp_bytes, key_a, key_b, idx_a, idx_b, N, s);
-        launch_hspchain_key_major(d_hsps, d_group, idx_b, N, key_a, s);
-        cover_sort_anchors(temp, &temp_bytes, key_a, key_b, idx_b, idx_a, N, s);
-        launch_hspchain_gather(d_hsps, d_group, idx_a, N, rs, qs, ln, sc, gr, head, s);
+        launch_hspchain_key_minor(d_hsps, N, d.key_a, idx_a, s);
+        cover_sort_anchors(temp, &d.temp_bytes, d.key_a, d.key_b, idx_a, d.idx_b, N, s);
+        launch_hspchain_key_major(d_hsps, d_group, d.idx_b, N, d.key_a, s);
+        cover_sort_anchors(temp, &d.temp_bytes, d.key_a, d.key_b, d.idx_b, idx_a, N, s);
+        launch_hspchain_gather(d_hsps, d_group, idx_a, N, rs, qs, ln, sc, gr, d.head, s);
         launch_hspchain_first(gr, N, T, first, s);
         check_launch("hspchain_rank");
     }
     ev.mark(1);
     check_memcpy(hipMemcpyAsync(h_first.data(), first, tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "hsp chain: first tiles");
     check_sync(s, "hspchain_rank");
-    const uint32_t* order = idx_a;
+    d.order = idx_a;
 
     // the DP: tile b after every tile before it
     ev.mark(2);
@@ -156,44 +155,83 @@ size_t sa_chain_hsps(const sa_segment_pair* hsps, size_t n, const uint32_t* grou
         st.pair_evals += (uint64_t)(b - c0) * T * nb + (uint64_t)nb * (nb - 1) / 2;
         st.tile_steps += (uint64_t)(b - c0) + 1;
     }
-    cover_scan_offsets(temp, &temp_bytes, head, gidx, N, s);
+    cover_scan_offsets(temp, &d.temp_bytes, d.head, d.gidx, N, s);
     ev.mark(3);
     uint64_t groups64 = 0;
-    check_memcpy(hipMemcpyAsync(&groups64, gidx + N, sizeof(uint64_t), hipMemcpyDeviceToHost, s), "hsp chain: groups");
+    check_memcpy(hipMemcpyAsync(&groups64, d.gidx + N, sizeof(uint64_t), hipMemcpyDeviceToHost, s), "hsp chain: groups");
     check_sync(s, "hspchain tiles");
-    const uint32_t G = (uint32_t)groups64;
+    d.G = (uint32_t)groups64;
+}
+
+// The checks both entries make before they touch the device.  Returns the tile.
+uint32_t checked(const sa_chain_params* p, size_t n, sa_chain_params& P) {
+    if (p) P = *p;
+    if (P.diag_pen < 0 || P.diag_pen > (1 << 20)) bad("diag_pen", P.diag_pen);
+    if (P.anti_pen < 0 || P.anti_pen > (1 << 20)) bad("anti_pen", P.anti_pen);
+    if (n > HSPCHAIN_MAX_N) bad("the number of HSPs", (long long)n);
+    const int64_t tile_opt = opt_value_now("chain_tile");
+    if (tile_opt < 64 || tile_opt > 1024 || (tile_opt & (tile_opt - 1))) bad("option chain_tile", tile_opt);
+    return (uint32_t)tile_opt;
+}
+
+void* host_array(size_t count, size_t size) {
+    if (!count) return nullptr;
+    void* p = malloc(count * size);
+    if (!p) {
+        fprintf(stderr, "Error: ChainHsps: out of host memory\n");
+        exit(12);
+    }
+    return p;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t sa_chain_hsps(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p, sa_chain_member** members,
+                     sa_chain_node** nodes, sa_chain_stats* stats) {
+    *members = nullptr;
+    if (nodes) *nodes = nullptr;
+    sa_chain_stats st;
+    memset(&st, 0, sizeof(st));
+    if (stats) *stats = st;
+    require_init("ChainHsps");
+    ChainDp d;
+    const uint32_t T = checked(p, n, d.P);
+    if (n == 0) return 0;
+    Slot* sl = d.sl = acquire_slot_early();
+    hipStream_t s = sl->stream;
+    Events ev(s, 8);
+    rank_and_dp(hsps, n, group, T, d, ev, st);
+    const uint32_t G = d.G;
 
     // finish: every group's end and chain length, then the members and the nodes
     ev.mark(4);
     {
         ProfScope ps(sl, "hspchain_finish");
-        launch_hspchain_group_starts(head, gidx, N, gstart, s);
-        launch_hspchain_ends(a, gstart, G, P.min_score, gend, glen, s);
-        cover_scan_offsets(temp, &temp_bytes, glen, goff, G, s);
+        launch_hspchain_group_starts(d.head, d.gidx, d.N, d.gstart, s);
+        launch_hspchain_ends(d.a, d.gstart, G, d.P.min_score, d.gend, d.glen, s);
+        cover_scan_offsets(d.temp, &d.temp_bytes, d.glen, d.goff, G, s);
         check_launch("hspchain_finish");
     }
     ev.mark(5);
     uint64_t total = 0;
-    check_memcpy(hipMemcpyAsync(&total, goff + G, sizeof(uint64_t), hipMemcpyDeviceToHost, s), "hsp chain: members");
+    check_memcpy(hipMemcpyAsync(&total, d.goff + G, sizeof(uint64_t), hipMemcpyDeviceToHost, s), "hsp chain: members");
     check_sync(s, "hspchain_finish");
     ev.mark(6);
     {
         ProfScope ps(sl, "hspchain_finish");
-        launch_hspchain_members(a, order, gend, glen, goff, G, d_members, s);
-        if (nodes) launch_hspchain_nodes(a, order, d_nodes, s);
+        launch_hspchain_members(d.a, d.order, d.gend, d.glen, d.goff, G, d.d_members, s);
+        if (nodes) launch_hspchain_nodes(d.a, d.order, d.d_nodes, s);
         check_launch("hspchain_finish");
     }
     ev.mark(7);
-    sa_chain_member* m_out = total ? (sa_chain_member*)malloc(total * sizeof(sa_chain_member)) : nullptr;
-    sa_chain_node* n_out = nodes ? (sa_chain_node*)malloc(n * sizeof(sa_chain_node)) : nullptr;
-    if ((total && !m_out) || (nodes && !n_out)) {
-        fprintf(stderr, "Error: ChainHsps: out of host memory\n");
-        exit(12);
-    }
-    if (total) check_memcpy(hipMemcpyAsync(m_out, d_members, total * sizeof(sa_chain_member), hipMemcpyDeviceToHost, s), "hsp chain: members");
-    if (nodes) check_memcpy(hipMemcpyAsync(n_out, d_nodes, n * sizeof(sa_chain_node), hipMemcpyDeviceToHost, s), "hsp chain: nodes");
+    sa_chain_member* m_out = (sa_chain_member*)host_array(total, sizeof(sa_chain_member));
+    sa_chain_node* n_out = nodes ? (sa_chain_node*)host_array(n, sizeof(sa_chain_node)) : nullptr;
+    if (total) check_memcpy(hipMemcpyAsync(m_out, d.d_members, total * sizeof(sa_chain_member), hipMemcpyDeviceToHost, s), "hsp chain: members");
+    if (nodes) check_memcpy(hipMemcpyAsync(n_out, d.d_nodes, n * sizeof(sa_chain_node), hipMemcpyDeviceToHost, s), "hsp chain: nodes");
     check_sync(s, "hspchain_finish");
-    st.kernel_ms = ev.total();
+    st.kernel_ms = ev.total(0, 4);
     prof_flush(sl);
     release_slot(sl);
 
@@ -211,6 +249,136 @@ size_t sa_chain_hsps(const sa_segment_pair* hsps, size_t n, const uint32_t* grou
 void sa_free_chain(sa_chain_member* members, sa_chain_node* nodes) {
     free(members);
     free(nodes);
+}
+
+size_t sa_chain_hsps_all(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p, sa_chain_record** chains,
+                         size_t* n_chains, sa_chain_all_member** members, sa_chain_node** nodes, uint32_t** chain_of,
+                         sa_chain_all_stats* stats) {
+    *chains = nullptr;
+    *n_chains = 0;
+    *members = nullptr;
+    if (nodes) *nodes = nullptr;
+    if (chain_of) *chain_of = nullptr;
+    sa_chain_all_stats st;
+    memset(&st, 0, sizeof(st));
+    if (stats) *stats = st;
+    require_init("ChainHsps");
+    ChainDp d;
+    const uint32_t T = checked(p, n, d.P);
+    if (n == 0) return 0;
+    Slot* sl = d.sl = acquire_slot_early();
+    hipStream_t s = sl->stream;
+    Events ev(s, 10);
+    rank_and_dp(hsps, n, group, T, d, ev, st.chain);
+    const uint32_t N = d.N;
+
+    HspPeelArgs a;
+    a.f = d.a.f; a.pred = d.a.pred; a.gr = d.a.gr; a.order = d.order;
+    a.n = N;
+    a.min_score = d.P.min_score;
+    a.key_a = d.key_a; a.key_b = d.key_b;  // free since the rank step
+    auto layout = [&](Take& t) {
+        t(a.idx_a, N); t(a.idx_b, N); t(a.byprio, N); t(a.val, N); t(a.ptr_a, N); t(a.ptr_b, N); t(a.head, N); t(a.cscore, N);
+        t(a.cjoin, N); t(a.corder, N); t(a.cpos, N); t(a.keep, (size_t)N + 1); t(a.kidx, (size_t)N + 1); t(a.khead, N);
+        t(a.first, (size_t)N + 1); t(a.tot, 3); t(a.chains, N); t(a.members, N); t(a.chain_of, N);
+    };
+    {
+        Take size{nullptr};
+        layout(size);
+        sl->hsppeel_work.ensure(size.end, "hsp peel");
+        Take t{sl->hsppeel_work.p};
+        layout(t);
+    }
+    uint32_t rounds = 1;
+    while (rounds < 32 && ((uint64_t)1 << rounds) < N) rounds++;  // max(1, ceil(log2 n)): a pred walk has fewer than n links
+
+    ev.mark(4);
+    {
+        ProfScope ps(sl, "hsppeel_subtree");
+        launch_hsppeel_prio_key(a, s);
+        cover_sort_anchors(d.temp, &d.temp_bytes, a.key_a, a.key_b, a.idx_a, a.byprio, N, s);  // stable: equal f stay in rank order
+        launch_hsppeel_init(a, s);
+        const uint32_t* ptr = a.pred;
+        for (uint32_t k = 0; k < rounds; k++) {
+            uint32_t* next = (k & 1) ? a.ptr_b : a.ptr_a;
+            launch_hsppeel_round(a, ptr, next, s);
+            ptr = next;
+        }
+        launch_hsppeel_tails(a, s);
+        check_launch("hsppeel_subtree");
+    }
+    ev.mark(5);
+    ev.mark(6);
+    {
+        ProfScope ps(sl, "hsppeel_order");
+        // the chains by (group, score descending, head rank): the minor sort starts from rank order, both sorts are stable
+        launch_hsppeel_chain_key_minor(a, s);
+        cover_sort_anchors(d.temp, &d.temp_bytes, a.key_a, a.key_b, a.idx_a, a.idx_b, N, s);
+        launch_hsppeel_chain_key_major(a, a.idx_b, s);
+        cover_sort_anchors(d.temp, &d.temp_bytes, a.key_a, a.key_b, a.idx_b, a.corder, N, s);
+        launch_hsppeel_keep(a, s);
+        cover_scan_offsets(d.temp, &d.temp_bytes, a.keep, a.kidx, N, s);
+        launch_hsppeel_assign(a, s);
+        check_launch("hsppeel_order");
+    }
+    ev.mark(7);
+    ev.mark(8);
+    {
+        ProfScope ps(sl, "hsppeel_members");
+        // the nodes by chain: they start in rank order, so the stable sort leaves a chain's members in rank order
+        launch_hsppeel_node_key(a, s);
+        cover_sort_anchors(d.temp, &d.temp_bytes, a.key_a, a.key_b, a.idx_a, a.idx_b, N, s);
+        launch_hsppeel_members(a, a.key_b, a.idx_b, s);
+        launch_hsppeel_records(a, s);
+        if (nodes) launch_hspchain_nodes(d.a, d.order, d.d_nodes, s);
+        check_launch("hsppeel_members");
+    }
+    ev.mark(9);
+    uint64_t tot[3] = {0, 0, 0};
+    check_memcpy(hipMemcpyAsync(tot, a.tot, sizeof(tot), hipMemcpyDeviceToHost, s), "hsp peel: totals");
+    check_sync(s, "hsppeel");
+    const size_t K = (size_t)tot[0], M = (size_t)tot[1];
+    if (K > n || M > n || K > M || tot[2] < K || tot[2] > n) {
+        fprintf(stderr, "Error: ChainHsps: %llu chains of %llu with %llu members from %zu HSPs\n", (unsigned long long)tot[0],
+                (unsigned long long)tot[2], (unsigned long long)tot[1], n);
+        exit(15);
+    }
+    sa_chain_record* c_out = (sa_chain_record*)host_array(K, sizeof(sa_chain_record));
+    sa_chain_all_member* m_out = (sa_chain_all_member*)host_array(M, sizeof(sa_chain_all_member));
+    sa_chain_node* n_out = nodes ? (sa_chain_node*)host_array(n, sizeof(sa_chain_node)) : nullptr;
+    uint32_t* o_out = chain_of ? (uint32_t*)host_array(n, sizeof(uint32_t)) : nullptr;
+    if (K) check_memcpy(hipMemcpyAsync(c_out, a.chains, K * sizeof(sa_chain_record), hipMemcpyDeviceToHost, s), "hsp peel: chains");
+    if (M) check_memcpy(hipMemcpyAsync(m_out, a.members, M * sizeof(sa_chain_all_member), hipMemcpyDeviceToHost, s), "hsp peel: members");
+    if (nodes) check_memcpy(hipMemcpyAsync(n_out, d.d_nodes, n * sizeof(sa_chain_node), hipMemcpyDeviceToHost, s), "hsp peel: nodes");
+    if (chain_of) check_memcpy(hipMemcpyAsync(o_out, a.chain_of, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "hsp peel: chain_of");
+    check_sync(s, "hsppeel");
+    st.chain.kernel_ms = ev.total(0, 2);
+    st.peel_ms = ev.total(2, 3);
+    prof_flush(sl);
+    release_slot(sl);
+
+    st.chain.hsps = n;
+    st.chain.groups = d.G;
+    st.chain.chains = K;
+    st.chain.members = M;
+    st.chains_all = tot[2];
+    st.peel_rounds = rounds;
+    for (size_t k = 0; k < K; k++)
+        if (c_out[k].joined >= 0) st.joined++;
+    if (stats) *stats = st;
+    *chains = c_out;
+    *n_chains = K;
+    *members = m_out;
+    if (nodes) *nodes = n_out;
+    if (chain_of) *chain_of = o_out;
+    return M;
+}
+
+void sa_free_chain_all(sa_chain_record* chains, sa_chain_all_member* members, sa_chain_node* nodes, uint32_t* chain_of) {
+    free(chains);
+    free(members);
+    free(nodes);
+    free(chain_of);
 }
 
 }  // extern "C"

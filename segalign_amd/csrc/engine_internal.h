@@ -12,7 +12,7 @@
 //   api_calls.hip      SeedAndFilter and its additive forms (range, chunks, interval, call lists), ExtendHits, DeviceMakeSeeds
 //   api_rm.hip         repeat-masker entries and the device-side coverage post-processing
 //   api_gapped.hip     sa_gapped_extend / _align / _align_greedy: gapped extension of HSP anchors, paths, cover (gapped.hip, cover.hip)
-//   api_hspchain.hip   sa_chain_hsps: the best collinear chain of every group of HSPs (hspchain.hip)
+//   api_hspchain.hip   sa_chain_hsps: the best collinear chain of every group of HSPs (hspchain.hip); sa_chain_hsps_all: all chains (hsppeel.hip)
 //   api_introspect.hip statistics, lookup mode, copies of device state for the tests
 #pragma once
 #include <hip/hip_runtime.h>
@@ -340,6 +340,7 @@ struct Slot {
     // sa_chain_hsps (api_hspchain.hip, hspchain.hip): the ranked HSPs with f and pred, sort keys and finish arrays, the cross launches'
     // partial bests, rocPRIM's temporary storage
     DevBuf<uint8_t> hspchain_work, hspchain_partial, hspchain_temp;
+    DevBuf<uint8_t> hsppeel_work;     // sa_chain_hsps_all (api_hspchain.hip, hsppeel.hip): everything the peel adds to the above
     bool early = false;               // taken from the pool that serves sa_chain_hsps before InitializeProcessor (pool.hip)
 };
 

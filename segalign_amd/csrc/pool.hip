@@ -130,6 +130,7 @@ void slot_destroy(Slot& s) {
     s.hspchain_work.release("hsp chain");
     s.hspchain_partial.release("hsp chain partials");
     s.hspchain_temp.release("hsp chain temp");
+    s.hsppeel_work.release("hsp peel");
     s.cand_list.release("candidate list");
     s.l2_list.release("second-level list");
     s.audit.release("audit list");

@@ -39,7 +39,7 @@ C_ABI_SYMBOLS = [
     "sa_get_lookup_mode", "sa_get_neighbourhood_entries",
     "sa_seed_calls", "sa_count_call_hits", "sa_count_chunk_hits", "sa_get_wga_chunk", "sa_release_arena", "sa_set_option", "sa_reset_option", "sa_get_option", "sa_option_count", "sa_option_name", "sa_get_audit",
     "sa_gapped_extend", "sa_free_gapped", "sa_gapped_align", "sa_free_gapped_align", "sa_gapped_align_greedy",
-    "sa_chain_hsps", "sa_free_chain",
+    "sa_chain_hsps", "sa_free_chain", "sa_chain_hsps_all", "sa_free_chain_all",
 ]
 IVL_DTYPE = np.dtype([("query_start", "<u4"), ("len", "<u4")])  # struct Segment, repeat_masker_src/graph.h:32-35
 STRAND_PLUS, STRAND_MINUS, STRAND_BOTH = 1, 2, 3
@@ -78,6 +78,10 @@ class GappedGreedyStats(C.Structure):
 
 CHAIN_MEMBER_DTYPE = np.dtype([("hsp_index", "<u4"), ("group", "<u4"), ("f", "<i8")])  # sa_chain_member
 CHAIN_NODE_DTYPE = np.dtype([("f", "<i8"), ("pred", "<i4"), ("pad", "<u4")])  # sa_chain_node
+CHAIN_RECORD_DTYPE = np.dtype([("group", "<u4"), ("head", "<u4"), ("first_member", "<u4"), ("n_members", "<u4"), ("score", "<i8"),
+                               ("joined", "<i4"), ("pad", "<u4")])  # sa_chain_record
+CHAIN_ALL_MEMBER_DTYPE = np.dtype([("hsp_index", "<u4"), ("group", "<u4"), ("chain", "<u4"), ("pad", "<u4"), ("f", "<i8")])  # sa_chain_all_member
+CHAIN_NONE = 0xFFFFFFFF  # chain_of of a member of a chain dropped by min_score
 
 
 class ChainParams(C.Structure):
@@ -87,6 +91,10 @@ class ChainParams(C.Structure):
 class ChainStats(C.Structure):
     _fields_ = [("hsps", C.c_uint64), ("groups", C.c_uint64), ("chains", C.c_uint64), ("members", C.c_uint64), ("pair_evals", C.c_uint64),
                 ("tile_steps", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
+class ChainAllStats(C.Structure):
+    _fields_ = [("chain", ChainStats), ("chains_all", C.c_uint64), ("joined", C.c_uint64), ("peel_rounds", C.c_uint64), ("peel_ms", C.c_double)]
 
 
 class CallStats(C.Structure):
@@ -196,6 +204,10 @@ def lib():
     L.sa_chain_hsps.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(ChainParams), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                 C.POINTER(ChainStats)]
     L.sa_free_chain.argtypes = [C.c_void_p, C.c_void_p]
+    L.sa_chain_hsps_all.restype = C.c_size_t
+    L.sa_chain_hsps_all.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(ChainParams), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                    C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(ChainAllStats)]
+    L.sa_free_chain_all.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -431,26 +443,49 @@ def GappedAlignGreedy(hsps, rev, buffer, gap_open=400, gap_extend=30, ydrop=9430
     return (*res, _flat(st))
 
 
-def ChainHsps(hsps, groups=None, diag_pen=0, anti_pen=0, max_gap=0, min_score=0, nodes=False):
-    """The best collinear chain of every group of HSPs (sa_chain_hsps; contract in include/segalign_amd.h, DESIGN.md 15).
-    hsps: SEG_DTYPE records; groups: one uint32 per HSP (None: all in group 0).  -> (CHAIN_MEMBER_DTYPE members, stats dict), or with
-    nodes=True (members, CHAIN_NODE_DTYPE nodes in input order, stats dict).  Needs InitializeInterface only."""
+def _chain_input(hsps, groups, diag_pen, anti_pen, max_gap, min_score):
     h = np.ascontiguousarray(hsps, dtype=SEG_DTYPE)
     g = None if groups is None else np.ascontiguousarray(groups, dtype=np.uint32)
     if g is not None and g.shape != h.shape:
         raise ValueError("groups: one entry per HSP")
-    p = ChainParams(int(diag_pen), int(anti_pen), int(max_gap), 0, int(min_score))
+    return h, g, ChainParams(int(diag_pen), int(anti_pen), int(max_gap), 0, int(min_score))
+
+
+def _chain_take(ptr, count, dtype):
+    """A copy of count records at a malloc-ed result pointer."""
+    dtype = np.dtype(dtype)
+    if not count or not ptr.value:
+        return np.zeros(0, dtype=dtype)
+    return np.frombuffer((C.c_char * (count * dtype.itemsize)).from_address(ptr.value), dtype=dtype).copy()
+
+
+def ChainHsps(hsps, groups=None, diag_pen=0, anti_pen=0, max_gap=0, min_score=0, nodes=False):
+    """The best collinear chain of every group of HSPs (sa_chain_hsps; contract in include/segalign_amd.h, DESIGN.md 15).
+    hsps: SEG_DTYPE records; groups: one uint32 per HSP (None: all in group 0).  -> (CHAIN_MEMBER_DTYPE members, stats dict), or with
+    nodes=True (members, CHAIN_NODE_DTYPE nodes in input order, stats dict).  Needs InitializeInterface only."""
+    h, g, p = _chain_input(hsps, groups, diag_pen, anti_pen, max_gap, min_score)
     mem, nod, st = C.c_void_p(), C.c_void_p(), ChainStats()
     m = lib().sa_chain_hsps(h.ctypes.data if h.size else None, h.size, g.ctypes.data if g is not None and g.size else None, C.byref(p),
                             C.byref(mem), C.byref(nod) if nodes else None, C.byref(st))
-
-    def take(ptr, count, dtype):
-        if not count or not ptr.value:
-            return np.zeros(0, dtype=dtype)
-        return np.frombuffer((C.c_char * (count * dtype.itemsize)).from_address(ptr.value), dtype=dtype).copy()
-    res_m, res_n = take(mem, m, CHAIN_MEMBER_DTYPE), take(nod, h.size, CHAIN_NODE_DTYPE)
+    res_m, res_n = _chain_take(mem, m, CHAIN_MEMBER_DTYPE), _chain_take(nod, h.size, CHAIN_NODE_DTYPE)
     lib().sa_free_chain(mem, nod)
     return (res_m, res_n, _flat(st)) if nodes else (res_m, _flat(st))
+
+
+def ChainHspsAll(hsps, groups=None, diag_pen=0, anti_pen=0, max_gap=0, min_score=0, nodes=False):
+    """All collinear chains of every group of HSPs, peeled best first (sa_chain_hsps_all; contract in include/segalign_amd.h,
+    DESIGN.md 16).  Arguments as ChainHsps.  -> (CHAIN_RECORD_DTYPE chains, CHAIN_ALL_MEMBER_DTYPE members, uint32 chain_of in input
+    order (CHAIN_NONE: the HSP's chain scores below min_score), stats dict); with nodes=True the CHAIN_NODE_DTYPE nodes come before
+    chain_of.  Needs InitializeInterface only."""
+    h, g, p = _chain_input(hsps, groups, diag_pen, anti_pen, max_gap, min_score)
+    ch, mem, nod, cof, st, nc = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), ChainAllStats(), C.c_size_t(0)
+    m = lib().sa_chain_hsps_all(h.ctypes.data if h.size else None, h.size, g.ctypes.data if g is not None and g.size else None,
+                                C.byref(p), C.byref(ch), C.byref(nc), C.byref(mem), C.byref(nod) if nodes else None, C.byref(cof),
+                                C.byref(st))
+    res_c, res_m = _chain_take(ch, nc.value, CHAIN_RECORD_DTYPE), _chain_take(mem, m, CHAIN_ALL_MEMBER_DTYPE)
+    res_n, res_o = _chain_take(nod, h.size, CHAIN_NODE_DTYPE), _chain_take(cof, h.size, np.uint32)
+    lib().sa_free_chain_all(ch, mem, nod, cof)
+    return (res_c, res_m, res_n, res_o, _flat(st)) if nodes else (res_c, res_m, res_o, _flat(st))
 
 
 def cigar(ops):

@@ -46,6 +46,9 @@ struct Config {  // src/graph.h:32-76 with the defaults of src/main.cpp:61-124
     bool gpu_chain = false;   // --gpu_chain[=diag,anti]: a .chain file next to every .segments file (sa_chain_hsps); the gapped entries get its HSPs only
     int chain_diag = 0, chain_anti = 0;  // sa_chain_params.diag_pen / anti_pen
     uint32_t chain_gap = 0;   // --gpu_chain_gap=N: sa_chain_params.max_gap; 0: unlimited
+    bool gpu_chain_all = false;  // --gpu_chain_all[=diag,anti]: a .chains file with all chains (sa_chain_hsps_all); the gapped entries get the kept chains' HSPs
+    bool chain_min_set = false;
+    long long chain_min = 0;  // --gpu_chain_min=N: sa_chain_params.min_score of --gpu_chain_all
     int gap_open = 400, gap_extend = 30;
     int xdrop = 910, hspthresh = 3000, ydrop = 9430, gappedthresh = -1;
     uint32_t wga_chunk = 250000, lastz_interval = 10000000, seq_block_size = 500000000;
@@ -239,11 +242,12 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
         if (!rev) for (size_t i = 0; i < v.size(); i++) emit(v[i]);
         else for (size_t i = v.size(); i-- > 0;) emit(v[i]);  // :130: reverse vector order on the minus strand
         fclose(f);
-        std::vector<sa_segment_pair> kept;  // with --gpu_chain: the chains' HSPs in their order within v
-        if (cfg.gpu_chain) {  // the best collinear chain of every (target record, query record) pair of this file, DESIGN.md 15
+        std::vector<sa_segment_pair> kept;  // with --gpu_chain or --gpu_chain_all: the chains' HSPs in their order within v
+        if (cfg.gpu_chain || cfg.gpu_chain_all) {  // chains within every (target record, query record) pair of this file, DESIGN.md 15 and 16
+            const char* flag = cfg.gpu_chain ? "--gpu_chain" : "--gpu_chain_all";
             if (v.size() > ((size_t)1 << 22))  // sa_chain_hsps' limit, told in the host's words
             {
-                fprintf(stderr, "--gpu_chain: %s holds %zu HSPs, more than the 4194304 one chaining call takes; lower --lastz_interval\n", seg_name.c_str(), v.size());
+                fprintf(stderr, "%s: %s holds %zu HSPs, more than the 4194304 one chaining call takes; lower --lastz_interval\n", flag, seg_name.c_str(), v.size());
                 exit(8);
             }
             std::vector<uint64_t> rec_pair(v.size());
@@ -254,21 +258,36 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
             pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
             std::vector<uint32_t> group(v.size());
             for (size_t i = 0; i < v.size(); i++) group[i] = (uint32_t)(std::lower_bound(pairs.begin(), pairs.end(), rec_pair[i]) - pairs.begin());
-            sa_chain_params cp = {cfg.chain_diag, cfg.chain_anti, cfg.chain_gap, 0, 0};
-            sa_chain_member* mem = nullptr;
-            const size_t nm = sa_chain_hsps(v.data(), v.size(), group.data(), &cp, &mem, nullptr, nullptr);
-            std::string cname = base + ".chain";
+            sa_chain_params cp = {cfg.chain_diag, cfg.chain_anti, cfg.chain_gap, 0, cfg.gpu_chain_all ? (int64_t)cfg.chain_min : 0};
+            std::string cname = base + (cfg.gpu_chain ? ".chain" : ".chains");
             f = fopen((cfg.outdir + "/" + cname).c_str(), "w");
             if (!f) die(7, "cant open file: %s", cname.c_str());
-            std::vector<uint32_t> idx(nm);
-            for (size_t k = 0; k < nm; k++) { emit(v[mem[k].hsp_index]); idx[k] = mem[k].hsp_index; }  // the order sa_chain_hsps returns, on both strands
+            std::vector<uint32_t> idx;
+            if (cfg.gpu_chain) {
+                sa_chain_member* mem = nullptr;
+                const size_t nm = sa_chain_hsps(v.data(), v.size(), group.data(), &cp, &mem, nullptr, nullptr);
+                idx.resize(nm);
+                for (size_t k = 0; k < nm; k++) { emit(v[mem[k].hsp_index]); idx[k] = mem[k].hsp_index; }  // the order sa_chain_hsps returns, on both strands
+                sa_free_chain(mem, nullptr);
+            } else {
+                sa_chain_record* ch = nullptr;
+                sa_chain_all_member* mem = nullptr;
+                size_t nc = 0;
+                const size_t nm = sa_chain_hsps_all(v.data(), v.size(), group.data(), &cp, &ch, &nc, &mem, nullptr, nullptr, nullptr);
+                idx.resize(nm);
+                for (size_t c = 0; c < nc; c++) {  // the order sa_chain_hsps_all returns, on both strands
+                    fprintf(f, "#chain %zu group=%u score=%lld members=%u joined=%d\n", c, ch[c].group, (long long)ch[c].score, ch[c].n_members,
+                            ch[c].joined >= 0 ? 1 : 0);
+                    for (size_t k = ch[c].first_member; k < (size_t)ch[c].first_member + ch[c].n_members; k++) { emit(v[mem[k].hsp_index]); idx[k] = mem[k].hsp_index; }
+                }
+                sa_free_chain_all(ch, mem, nullptr, nullptr);
+            }
             fclose(f);
-            sa_free_chain(mem, nullptr);
             std::sort(idx.begin(), idx.end());  // an HSP is a member of one chain at most: no duplicates
-            kept.reserve(nm);
+            kept.reserve(idx.size());
             for (uint32_t i : idx) kept.push_back(v[i]);
         }
-        const std::vector<sa_segment_pair>& anchors = cfg.gpu_chain ? kept : v;  // what the gapped entries extend
+        const std::vector<sa_segment_pair>& anchors = (cfg.gpu_chain || cfg.gpu_chain_all) ? kept : v;  // what the gapped entries extend
         if (cfg.gpu_gapped) {  // the gapped extension of the same HSPs on the device: [start, end) extents printed like the segments
             sa_gapped_params gp = {cfg.gap_open, cfg.gap_extend, cfg.ydrop, cfg.gappedthresh, cfg.gpu_max_extent, 0};
             sa_gapped_alignment* al = nullptr;
@@ -357,7 +376,11 @@ static void usage() {
             "  --gpu_chain[=diag,anti] (a .chain file next to each .segments file: the best collinear chain of every target record x query\n"
             "      record pair, with penalties per diagonal and antidiagonal step, default 0,0; --gpu_gapped then extends the chains' HSPs only)\n"
             "  --gpu_chain_gap=N (with --gpu_chain: largest gap between consecutive chain members in either sequence; default 0, unlimited)\n"
-            "      a .segments file may hold at most 4194304 HSPs with --gpu_chain\n");
+            "      a .segments file may hold at most 4194304 HSPs with --gpu_chain\n"
+            "  --gpu_chain_all[=diag,anti] (instead of --gpu_chain: a .chains file next to each .segments file with ALL collinear chains of\n"
+            "      every pair, peeled best first, each under a line '#chain k group=g score=s members=m joined=0|1'; takes --gpu_chain_gap and\n"
+            "      the same limit; --gpu_gapped then extends the HSPs of the chains kept)\n"
+            "  --gpu_chain_min=N (with --gpu_chain_all: chains that score less than N are not kept; default 0)\n");
 }
 
 int main(int argc, char** argv) {
@@ -405,6 +428,19 @@ int main(int argc, char** argv) {
             if (sscanf(v.c_str(), "%d,%d%c", &cfg.chain_diag, &cfg.chain_anti, &tail) != 2 || cfg.chain_diag < 0 || cfg.chain_diag > (1 << 20) ||
                 cfg.chain_anti < 0 || cfg.chain_anti > (1 << 20)) { fprintf(stderr, "bad --gpu_chain=%s (diag,anti; each 0 .. %d)\n", v.c_str(), 1 << 20); return 1; }
         }
+        else if (!strcmp(a, "--gpu_chain_all")) cfg.gpu_chain_all = true;
+        else if (opt(a, "--gpu_chain_all", v)) {
+            cfg.gpu_chain_all = true;
+            char tail;
+            if (sscanf(v.c_str(), "%d,%d%c", &cfg.chain_diag, &cfg.chain_anti, &tail) != 2 || cfg.chain_diag < 0 || cfg.chain_diag > (1 << 20) ||
+                cfg.chain_anti < 0 || cfg.chain_anti > (1 << 20)) { fprintf(stderr, "bad --gpu_chain_all=%s (diag,anti; each 0 .. %d)\n", v.c_str(), 1 << 20); return 1; }
+        }
+        else if (opt(a, "--gpu_chain_min", v)) {
+            char* endp = nullptr;
+            cfg.chain_min = strtoll(v.c_str(), &endp, 10);
+            if (endp == v.c_str() || *endp) { fprintf(stderr, "bad --gpu_chain_min=%s (an integer)\n", v.c_str()); return 1; }
+            cfg.chain_min_set = true;
+        }
         else if (opt(a, "--gpu_chain_gap", v)) {
             char* endp = nullptr;
             const long long gap = strtoll(v.c_str(), &endp, 10);
@@ -421,6 +457,8 @@ int main(int argc, char** argv) {
         usage();
         return 1;
     }
+    if (cfg.gpu_chain && cfg.gpu_chain_all) { fprintf(stderr, "--gpu_chain and --gpu_chain_all exclude each other\n"); return 1; }
+    if (cfg.chain_min_set && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_chain_min needs --gpu_chain_all\n"); return 1; }
     cfg.target = pos[0];
     cfg.query = pos[1];
     if (pos.size() > 2) cfg.data_folder = pos[2];

@@ -14,8 +14,13 @@ members kept, pair evaluations, tile steps, the chain kernel ms and pair evaluat
 --greedy also the alignment / greedy) times on the chain's members beside those on all HSPs.  f and pred of every HSP and the members
 are checked against the numpy model (tests/hsp_chain_model.py) once per run.
 
+With --chain-all [--chain-min N] (which implies --chain) the HSPs also go through sa_chain_hsps_all: the line then adds
+the chains before min_score, the chains, joined chains and members kept, the doubling rounds, peel ms beside the DP's kernel ms, and
+the gapped times on the kept chains' members beside those on the best chain and on all HSPs.  The chains, members and chain_of are
+checked against the numpy model (tests/hsp_chain_all_model.py) once per run, on the f and pred the --chain check computed.
+
   python tools/gapped_bench.py [--workloads standin,lumpy] [--repeat 3] [--align] [--greedy] [--batches 1024,2048,...]
-                               [--pieces N] [--max-extent M] [--chain] [--chain-pen D,A]
+                               [--pieces N] [--max-extent M] [--chain] [--chain-pen D,A] [--chain-all] [--chain-min N]
 """
 import argparse
 import functools
@@ -139,8 +144,48 @@ def greedy_fields(hsps, repeat, with_sel=True):
             "trace_mb": int(E.get_option("gapped_trace_mb")), "greedy_ops": int(gops.size)}
 
 
-def chain_fields(hsps, repeat, pen, align, greedy):
-    """sa_chain_hsps on the HSPs as one group, checked against the numpy model, and the gapped entries on the chain's members."""
+def kept_fields(kept, repeat, align, greedy, prefix):
+    """The gapped entries on the HSPs a chaining step kept."""
+    kst = min((E.GappedExtend(kept, False, 0, **KW)[1] for _ in range(repeat)), key=lambda x: x["kernel_ms"])
+    out = {prefix + "extend_ms": round(kst["kernel_ms"], 3), prefix + "cells": int(kst["cells"]), prefix + "alignments": int(kst["returned"])}
+    if align:
+        ast = min((E.GappedAlign(kept, False, 0, **KW)[3] for _ in range(repeat)), key=lambda x: x["kernel_ms"] + x["trace_ms"] + x["walk_ms"])
+        out[prefix + "align_kernel_ms"] = round(ast["kernel_ms"] + ast["trace_ms"] + ast["walk_ms"], 3)
+    if greedy:
+        gst = min((E.GappedAlignGreedy(kept, False, 0, **KW)[3] for _ in range(repeat)),
+                  key=lambda x: x["kernel_ms"] + x["trace_ms"] + x["walk_ms"] + x["cover_ms"])
+        out[prefix + "greedy_kernel_ms"] = round(gst["kernel_ms"] + gst["trace_ms"] + gst["walk_ms"] + gst["cover_ms"], 3)
+    return out
+
+
+def chain_all_fields(hsps, repeat, pen, min_score, dp, align, greedy):
+    """sa_chain_hsps_all on the HSPs as one group, checked against the numpy model on the DP values `dp` that chain_fields checked, and
+    the gapped entries on the kept chains' members."""
+    import hsp_chain_all_model as A
+    best = None
+    for _ in range(repeat):
+        t0 = time.perf_counter()
+        r = E.ChainHspsAll(hsps, None, diag_pen=pen[0], anti_pen=pen[1], min_score=min_score, nodes=True)
+        wall = (time.perf_counter() - t0) * 1e3
+        if best is None or r[4]["peel_ms"] < best[0][4]["peel_ms"]:
+            best = (r, wall)
+    (chains, members, nodes, chain_of, st), wall = best
+    f, pred, want_c, want_m, want_of = A.chain_all(hsps, None, diag_pen=pen[0], anti_pen=pen[1], min_score=min_score, dp=dp)
+    if not (np.array_equal(nodes["f"], f) and np.array_equal(nodes["pred"], pred) and np.array_equal(chains, want_c.astype(chains.dtype))
+            and np.array_equal(members, want_m.astype(members.dtype)) and np.array_equal(chain_of, want_of)):
+        raise SystemExit("sa_chain_hsps_all differs from the numpy model")
+    out = {"all_min_score": int(min_score), "all_chains_before_min": int(st["chains_all"]), "all_chains": int(st["chains"]),
+           "all_joined": int(st["joined"]), "all_members": int(st["members"]), "peel_rounds": int(st["peel_rounds"]),
+           "peel_ms": round(st["peel_ms"], 3), "all_dp_kernel_ms": round(st["kernel_ms"], 3),
+           "peel_over_dp": round(st["peel_ms"] / st["kernel_ms"], 4) if st["kernel_ms"] > 0 else None, "all_call_ms": round(wall, 3),
+           "all_model_checked": True}
+    out.update(kept_fields(hsps[np.sort(members["hsp_index"])], repeat, align, greedy, "all_kept_"))
+    return out
+
+
+def chain_fields(hsps, repeat, pen, align, greedy, all_min=None):
+    """sa_chain_hsps on the HSPs as one group, checked against the numpy model, and the gapped entries on the chain's members; with
+    all_min also chain_all_fields."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import hsp_chain_model as M
     best = None
@@ -162,19 +207,13 @@ def chain_fields(hsps, repeat, pen, align, greedy):
            "chain_tile_steps": int(st["tile_steps"]), "chain_tile": int(E.get_option("chain_tile")), "chain_kernel_ms": round(st["kernel_ms"], 3),
            "chain_call_ms": round(wall, 3), "chain_gpairs_per_s": round(st["pair_evals"] / (st["kernel_ms"] * 1e-3) / 1e9, 3) if st["kernel_ms"] > 0 else None,
            "chain_model_checked": True, "chain_model_s": round(model_s, 1)}
-    kst = min((E.GappedExtend(kept, False, 0, **KW)[1] for _ in range(repeat)), key=lambda x: x["kernel_ms"])
-    out.update({"kept_extend_ms": round(kst["kernel_ms"], 3), "kept_cells": int(kst["cells"]), "kept_alignments": int(kst["returned"])})
-    if align:
-        ast = min((E.GappedAlign(kept, False, 0, **KW)[3] for _ in range(repeat)), key=lambda x: x["kernel_ms"] + x["trace_ms"] + x["walk_ms"])
-        out["kept_align_kernel_ms"] = round(ast["kernel_ms"] + ast["trace_ms"] + ast["walk_ms"], 3)
-    if greedy:
-        gst = min((E.GappedAlignGreedy(kept, False, 0, **KW)[3] for _ in range(repeat)),
-                  key=lambda x: x["kernel_ms"] + x["trace_ms"] + x["walk_ms"] + x["cover_ms"])
-        out["kept_greedy_kernel_ms"] = round(gst["kernel_ms"] + gst["trace_ms"] + gst["walk_ms"] + gst["cover_ms"], 3)
+    out.update(kept_fields(kept, repeat, align, greedy, "kept_"))
+    if all_min is not None:
+        out.update(chain_all_fields(hsps, repeat, pen, all_min, (f, pred), align, greedy))
     return out
 
 
-def run(name, repeat, align=False, greedy=False, with_sel=True, pieces=0, chain=None):
+def run(name, repeat, align=False, greedy=False, with_sel=True, pieces=0, chain=None, chain_all_min=None):
     t, q = workload(name)
     if greedy or pieces:
         E.set_option("debug", 1)  # sa_gapped_align_greedy then prints its edge count, the continuation its pieces
@@ -222,7 +261,7 @@ def run(name, repeat, align=False, greedy=False, with_sel=True, pieces=0, chain=
     if greedy:
         extra.update(greedy_fields(hsps, repeat, with_sel))
     if chain is not None:
-        extra.update(chain_fields(hsps, repeat, chain, align, greedy))
+        extra.update(chain_fields(hsps, repeat, chain, align, greedy, chain_all_min))
     E.ShutdownProcessor()
     if greedy or pieces:
         E.reset_option("debug")
@@ -246,13 +285,15 @@ def main():
     ap.add_argument("--max-extent", type=int, default=0, help="max_extent of every entry (0: the default, 65536)")
     ap.add_argument("--chain", action="store_true", help="also chain the HSPs (sa_chain_hsps) and time the gapped entries on the chain's members")
     ap.add_argument("--chain-pen", default="0,0", help="with --chain: diag_pen,anti_pen")
+    ap.add_argument("--chain-all", action="store_true", help="also peel the HSPs into all chains (sa_chain_hsps_all); implies --chain")
+    ap.add_argument("--chain-min", type=int, default=0, help="with --chain-all: min_score")
     a = ap.parse_args()
-    chain = tuple(int(x) for x in a.chain_pen.split(",")) if a.chain else None
+    chain = tuple(int(x) for x in a.chain_pen.split(",")) if a.chain or a.chain_all else None
     if a.max_extent:
         KW["max_extent"] = a.max_extent
     for name in a.workloads.split(","):
         if not a.batches:
-            print(json.dumps(run(name, a.repeat, a.align, a.greedy, pieces=a.pieces, chain=chain)), flush=True)
+            print(json.dumps(run(name, a.repeat, a.align, a.greedy, pieces=a.pieces, chain=chain, chain_all_min=a.chain_min if a.chain_all else None)), flush=True)
             continue
         for b in a.batches.split(","):
             E.set_option("gapped_greedy_batch", int(b))
