@@ -232,7 +232,8 @@ int sa_max_hits_for_mem(uint64_t total_global_mem);
  *   seed_upload       how sa_seed_and_filter brings the host seed vector over: 0 copy into a pinned staging buffer + DMA (default),
  *                     1 hipMemcpyAsync from the pageable vector (the runtime stages it), 2 hipHostRegister the vector + DMA
  *   gapped_trace_mb   MiB of trace area one sa_gapped_align batch packs its traced sides into (default 1024; a side that needs more
- *                     runs in a batch of its own and grows the slot's buffer to fit).  Each slot keeps its buffer until shutdown
+ *                     runs in a batch of its own and grows the slot's buffer to fit).  Each slot keeps its buffer until shutdown.
+ *                     sa_stitch_chains packs the trace areas of its links under the same budget, in a buffer of its own
  *   gapped_greedy_batch  anchors per priority batch of sa_gapped_align_greedy (default 1024; 1 .. 1 << 20).  Its records and its
  *                     covered / below_thresh counts do not depend on it; only skipped and the work done do
  *   gapped_greedy_edges  in-edges one resolve pass of sa_gapped_align_greedy holds (default 1 << 26, 4 bytes each; 1 .. 1 << 32).  Anchors
@@ -683,6 +684,111 @@ size_t sa_chain_hsps_all(const sa_segment_pair* hsps, size_t n, const uint32_t* 
                          size_t* n_chains, sa_chain_all_member** members, sa_chain_node** nodes, uint32_t** chain_of,
                          sa_chain_all_stats* stats);
 void sa_free_chain_all(sa_chain_record* chains, sa_chain_all_member* members, sa_chain_node* nodes, uint32_t* chain_of);
+
+/* ---- stitching the members of a chain into one gapped alignment (additive; restated by tests/cpp/stitch_check.c and
+ *      tests/stitch_model.py) ----------------------------------------------------------------------------------------------
+ *
+ * sa_stitch_chains turns every chain into the alignment that runs through all its members: the members as they are, and between two
+ * consecutive members a global affine alignment of the rectangle that separates them.  The semantics are this project's own and are
+ * NOT claimed to equal LASTZ's or axtChain's.
+ *   Input: n_hsps HSPs (len = bases - 1; rs = ref_start, qs = query_start, re = rs + len + 1, qe = qs + len + 1) on strand `rev` of query
+ *     buffer `buffer`; chains in CSR form: chain c is members[first[c]] .. members[first[c + 1] - 1], each an index into hsps, first[0] = 0,
+ *     first[] non-decreasing, at most 1 << 22 members in total (an HSP may be a member of several chains; an empty chain gives no record).
+ *     The entry needs a resident target block and query buffer, like the gapped entries, and gives their error without them.
+ *   Validation (a message and exit code 1, like the gapped and chain entries): every member lies inside the block on both sequences
+ *     (re <= target length, qe <= query length); consecutive members m, m' of a chain satisfy re_m <= rs_m' and qe_m <= qs_m' (what the
+ *     ranks of sa_chain_hsps / sa_chain_hsps_all guarantee); gap_open, gap_extend in 0 .. 1 << 20, max_link <= 2048, and
+ *     2 O + 2 max_link (E_ext + A) < 1 << 29 with A the largest |sub_mat entry| over the codes 0 .. 6, which keeps every finite int32
+ *     cell above -(1 << 29): the headroom sa_gapped_extend relies on with its -(1 << 30) minus infinity.
+ *   Link between consecutive members m, m': the rectangle of the dt = rs_m' - re_m target bases from re_m by the dq = qs_m' - qe_m query
+ *     bases from qe_m.  With X[i] = T[re_m + i], Y[j] = Q[qe_m + j] its alignment follows the recurrence of sa_gapped_extend's right
+ *     side word for word -- H(0,0) = 0, E, F, M and H as above, separator cells dead -- with no y-drop and no band cap, the cells
+ *     confined to 0 <= i <= dt, 0 <= j <= dq, and the end cell fixed at (dt, dq) in state H instead of a best cell.
+ *     link_score = H(dt, dq).  The path walks back from there under sa_gapped_align's tie rules, unchanged: in state H take M if
+ *     H == M, otherwise E if H == E, otherwise F; in state E or F a tie opens.
+ *     Consequences: dt = dq = 0 gives score 0 and no op; dt = 0 or dq = 0 gives exactly one I or D run scoring -(O + k E_ext);
+ *     H(dt, dq) is not finite exactly when a separator (code 7) lies in either range.
+ *   Broken links, flagged: SA_STITCH_LONG when dt > max_link or dq > max_link (the link is not swept); SA_STITCH_DEAD when H(dt, dq) is
+ *     not finite; SA_STITCH_LOW when link_score is finite and < min_link_score.
+ *   Records: broken links cut a chain into runs of members; each run gives one record, ordered by chain, then by run.
+ *     first_member, n_members: positions within the chain; extents: the first member's start and the last member's end;
+ *     score (int64) = sum over the members of sum_k sub_mat[T[rs + k] * 8 + Q[qs + k]], recomputed from the codes (the HSP's score
+ *     field is not read; a separator inside a hand-built member scores as the matrix has it), plus the link_scores inside the run;
+ *     flags: the reason bit of the broken link that ends the run, 0 at the chain's end.
+ *   Ops: (run << 2) | op with SA_GAPPED_OP_M / _I / _D in genome order: each member is one M run of len + 1, each link's ops lie between
+ *     its members, adjacent runs with the same op are merged into one; a run is cut at (1 << 30) - 1 and continues in the next entry, the
+ *     only place where two neighbours share an op.  The ops consume exactly [ref_start, ref_end) x [query_start, query_end), and
+ *     re-scoring them -- sub_mat over the M pairs minus O + k E_ext per gap run -- gives score.  matches / mismatches count the M pairs
+ *     as sa_gapped_path does, gap_opens the I and D runs, gap_bases their bases.
+ *   On request one sa_stitch_link per consecutive pair, chain by chain in input order: score is link_score, 0 for a link that was not
+ *     swept and INT32_MIN for a dead one; cells = (dt + 1)(dq + 1), 0 for a link that was not swept.
+ * The device sweeps every link that is not SA_STITCH_LONG (one wavefront per link, the instance chosen by dt), walks those that are
+ * neither dead nor low with sa_gapped_align's walk kernel, and packs the links' trace areas into batches under option
+ * gapped_trace_mb (a larger link runs alone).  Slots and thread safety are the gapped entries'. */
+#define SA_STITCH_LONG 1u /* dt or dq above max_link: not aligned */
+#define SA_STITCH_DEAD 2u /* a separator in either range: no alignment exists */
+#define SA_STITCH_LOW 4u  /* link_score < min_link_score */
+
+typedef struct sa_stitch_params {
+    int32_t gap_open;       /* O, default 400; 0 .. 1 << 20 */
+    int32_t gap_extend;     /* E_ext, default 30; 0 .. 1 << 20 */
+    uint32_t max_link;      /* largest side of a link that is still aligned; 0 = 2048; at most 2048 */
+    int32_t min_link_score; /* a link scoring below it is broken; INT32_MIN (the default) = never */
+} sa_stitch_params;
+
+typedef struct sa_stitch_record { /* 72 bytes */
+    uint32_t chain;                  /* index of the chain */
+    uint32_t first_member, n_members; /* positions within the chain */
+    uint32_t flags;                  /* SA_STITCH_* of the broken link that ends the run; 0 at the chain's end */
+    uint32_t ref_start, ref_end;     /* the first member's start, the last member's end */
+    uint32_t query_start, query_end;
+    int64_t score;
+    uint64_t op_offset;              /* index of the record's first op in *ops */
+    uint32_t n_ops;
+    uint32_t matches, mismatches;    /* M pairs with equal codes < 4; all other M pairs */
+    uint32_t gap_opens, gap_bases;   /* I and D runs; bases in them */
+    uint32_t pad;
+} sa_stitch_record;
+
+typedef struct sa_stitch_link { /* 32 bytes */
+    uint32_t chain;
+    uint32_t member;  /* position in the chain of the member the link follows */
+    uint32_t dt, dq;
+    int32_t score;
+    uint32_t flags;   /* SA_STITCH_* or 0 */
+    uint64_t cells;
+} sa_stitch_link;
+
+typedef struct sa_stitch_stats {
+    uint64_t links;
+    uint64_t swept;        /* links that are not SA_STITCH_LONG */
+    uint64_t long_links, dead_links, low_links;
+    uint64_t cells;        /* summed over the swept links */
+    uint64_t records;
+    double member_ms;      /* device time of the member scores */
+    double sweep_ms;       /* device time of the sweeps */
+    double walk_ms;        /* device time of the path walks */
+    uint64_t trace_bytes;  /* trace bytes written, summed over the batches */
+    uint64_t batches;      /* batches the swept links with dt + dq > 0 were packed into (option gapped_trace_mb) */
+} sa_stitch_stats;
+#ifdef __cplusplus
+static_assert(sizeof(sa_stitch_params) == 16, "sa_stitch_params is 16 bytes");
+static_assert(sizeof(sa_stitch_record) == 72, "sa_stitch_record is 72 bytes");
+static_assert(sizeof(sa_stitch_link) == 32, "sa_stitch_link is 32 bytes");
+static_assert(sizeof(sa_stitch_stats) == 96, "sa_stitch_stats is 96 bytes");
+#else
+_Static_assert(sizeof(sa_stitch_params) == 16, "sa_stitch_params is 16 bytes");
+_Static_assert(sizeof(sa_stitch_record) == 72, "sa_stitch_record is 72 bytes");
+_Static_assert(sizeof(sa_stitch_link) == 32, "sa_stitch_link is 32 bytes");
+_Static_assert(sizeof(sa_stitch_stats) == 96, "sa_stitch_stats is 96 bytes");
+#endif
+
+/* Returns the number of records.  *records, *ops (*n_ops entries) and *links (*n_links entries; links and n_links nullable together) are
+ * malloc-ed and released with sa_free_stitch; each is NULL when it would be empty.  p: NULL takes the defaults.  stats: nullable. */
+size_t sa_stitch_chains(const sa_segment_pair* hsps, size_t n_hsps, const uint32_t* members, const uint32_t* first, size_t n_chains, int rev,
+                        uint32_t buffer, const sa_stitch_params* p, sa_stitch_record** records, uint32_t** ops, size_t* n_ops,
+                        sa_stitch_link** links, size_t* n_links, sa_stitch_stats* stats);
+void sa_free_stitch(sa_stitch_record* records, uint32_t* ops, sa_stitch_link* links);
 
 const char* sa_version(void);
 

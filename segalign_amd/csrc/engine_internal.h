@@ -341,6 +341,8 @@ struct Slot {
     // partial bests, rocPRIM's temporary storage
     DevBuf<uint8_t> hspchain_work, hspchain_partial, hspchain_temp;
     DevBuf<uint8_t> hsppeel_work;     // sa_chain_hsps_all (api_hspchain.hip, hsppeel.hip): everything the peel adds to the above
+    DevBuf<uint8_t> stitch;           // sa_stitch_chains (api_stitch.hip, stitch.hip): the members and their scores, then a batch's link tasks,
+                                      // scores, walk results, op areas and trace areas
     bool early = false;               // taken from the pool that serves sa_chain_hsps before InitializeProcessor (pool.hip)
 };
 

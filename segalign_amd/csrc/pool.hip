@@ -131,6 +131,7 @@ void slot_destroy(Slot& s) {
     s.hspchain_partial.release("hsp chain partials");
     s.hspchain_temp.release("hsp chain temp");
     s.hsppeel_work.release("hsp peel");
+    s.stitch.release("stitch");
     s.cand_list.release("candidate list");
     s.l2_list.release("second-level list");
     s.audit.release("audit list");

@@ -40,6 +40,7 @@ C_ABI_SYMBOLS = [
     "sa_seed_calls", "sa_count_call_hits", "sa_count_chunk_hits", "sa_get_wga_chunk", "sa_release_arena", "sa_set_option", "sa_reset_option", "sa_get_option", "sa_option_count", "sa_option_name", "sa_get_audit",
     "sa_gapped_extend", "sa_free_gapped", "sa_gapped_align", "sa_free_gapped_align", "sa_gapped_align_greedy",
     "sa_chain_hsps", "sa_free_chain", "sa_chain_hsps_all", "sa_free_chain_all",
+    "sa_stitch_chains", "sa_free_stitch",
 ]
 IVL_DTYPE = np.dtype([("query_start", "<u4"), ("len", "<u4")])  # struct Segment, repeat_masker_src/graph.h:32-35
 STRAND_PLUS, STRAND_MINUS, STRAND_BOTH = 1, 2, 3
@@ -95,6 +96,26 @@ class ChainStats(C.Structure):
 
 class ChainAllStats(C.Structure):
     _fields_ = [("chain", ChainStats), ("chains_all", C.c_uint64), ("joined", C.c_uint64), ("peel_rounds", C.c_uint64), ("peel_ms", C.c_double)]
+
+
+STITCH_RECORD_DTYPE = np.dtype([("chain", "<u4"), ("first_member", "<u4"), ("n_members", "<u4"), ("flags", "<u4"), ("ref_start", "<u4"),
+                                ("ref_end", "<u4"), ("query_start", "<u4"), ("query_end", "<u4"), ("score", "<i8"), ("op_offset", "<u8"),
+                                ("n_ops", "<u4"), ("matches", "<u4"), ("mismatches", "<u4"), ("gap_opens", "<u4"), ("gap_bases", "<u4"),
+                                ("pad", "<u4")])  # sa_stitch_record
+STITCH_LINK_DTYPE = np.dtype([("chain", "<u4"), ("member", "<u4"), ("dt", "<u4"), ("dq", "<u4"), ("score", "<i4"), ("flags", "<u4"),
+                              ("cells", "<u8")])  # sa_stitch_link
+STITCH_LONG, STITCH_DEAD, STITCH_LOW = 1, 2, 4
+STITCH_NEVER = -(1 << 31)  # min_link_score that breaks no link
+
+
+class StitchParams(C.Structure):
+    _fields_ = [("gap_open", C.c_int32), ("gap_extend", C.c_int32), ("max_link", C.c_uint32), ("min_link_score", C.c_int32)]
+
+
+class StitchStats(C.Structure):
+    _fields_ = [("links", C.c_uint64), ("swept", C.c_uint64), ("long_links", C.c_uint64), ("dead_links", C.c_uint64),
+                ("low_links", C.c_uint64), ("cells", C.c_uint64), ("records", C.c_uint64), ("member_ms", C.c_double),
+                ("sweep_ms", C.c_double), ("walk_ms", C.c_double), ("trace_bytes", C.c_uint64), ("batches", C.c_uint64)]
 
 
 class CallStats(C.Structure):
@@ -208,6 +229,11 @@ def lib():
     L.sa_chain_hsps_all.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(ChainParams), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                     C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(ChainAllStats)]
     L.sa_free_chain_all.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sa_stitch_chains.restype = C.c_size_t
+    L.sa_stitch_chains.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(StitchParams),
+                                   C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
+                                   C.POINTER(C.c_size_t), C.POINTER(StitchStats)]
+    L.sa_free_stitch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -486,6 +512,36 @@ def ChainHspsAll(hsps, groups=None, diag_pen=0, anti_pen=0, max_gap=0, min_score
     res_n, res_o = _chain_take(nod, h.size, CHAIN_NODE_DTYPE), _chain_take(cof, h.size, np.uint32)
     lib().sa_free_chain_all(ch, mem, nod, cof)
     return (res_c, res_m, res_n, res_o, _flat(st)) if nodes else (res_c, res_m, res_o, _flat(st))
+
+
+def chain_csr(members):
+    """The members ChainHsps (one chain per group) or ChainHspsAll (field chain) returns, as StitchChains takes them:
+    -> (members: uint32 HSP indices, first: uint32 offsets, one more than there are chains)."""
+    m = np.asarray(members)
+    key = m["chain"] if "chain" in m.dtype.names else m["group"]
+    starts = np.flatnonzero(np.concatenate([[True], key[1:] != key[:-1]])) if m.size else np.zeros(0, dtype=np.int64)
+    return m["hsp_index"].astype(np.uint32), np.concatenate([starts, [m.size]]).astype(np.uint32)
+
+
+def StitchChains(hsps, members, first, rev, buffer=0, gap_open=400, gap_extend=30, max_link=0, min_link_score=None, links=False):
+    """Every chain as one gapped alignment through all its members (sa_stitch_chains; contract in include/segalign_amd.h).
+    hsps: SEG_DTYPE records on strand `rev` of query `buffer`; chain c is members[first[c]:first[c + 1]] (see chain_csr).
+    -> (STITCH_RECORD_DTYPE records, uint32 ops, stats dict), with links=True (records, ops, STITCH_LINK_DTYPE links, stats dict).
+    Record k's ops are ops[op_offset:][:n_ops]; decode them with cigar()."""
+    h = np.ascontiguousarray(hsps, dtype=SEG_DTYPE)
+    m = np.ascontiguousarray(members, dtype=np.uint32)
+    f = np.ascontiguousarray(first, dtype=np.uint32)
+    if f.size < 1 or int(f[-1]) != m.size:
+        raise ValueError("first: one offset per chain and the number of members at the end")
+    p = StitchParams(int(gap_open), int(gap_extend), int(max_link), STITCH_NEVER if min_link_score is None else int(min_link_score))
+    rec, ops, lnk, n_ops, n_links, st = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t(0), C.c_size_t(0), StitchStats()
+    n = lib().sa_stitch_chains(h.ctypes.data if h.size else None, h.size, m.ctypes.data if m.size else None, f.ctypes.data, f.size - 1,
+                               int(bool(rev)), buffer, C.byref(p), C.byref(rec), C.byref(ops), C.byref(n_ops),
+                               C.byref(lnk) if links else None, C.byref(n_links) if links else None, C.byref(st))
+    res_r, res_o = _chain_take(rec, n, STITCH_RECORD_DTYPE), _chain_take(ops, n_ops.value, np.dtype("<u4"))
+    res_l = _chain_take(lnk, n_links.value, STITCH_LINK_DTYPE)
+    lib().sa_free_stitch(rec, ops, lnk)
+    return (res_r, res_o, res_l, _flat(st)) if links else (res_r, res_o, _flat(st))
 
 
 def cigar(ops):

@@ -49,6 +49,10 @@ struct Config {  // src/graph.h:32-76 with the defaults of src/main.cpp:61-124
     bool gpu_chain_all = false;  // --gpu_chain_all[=diag,anti]: a .chains file with all chains (sa_chain_hsps_all); the gapped entries get the kept chains' HSPs
     bool chain_min_set = false;
     long long chain_min = 0;  // --gpu_chain_min=N: sa_chain_params.min_score of --gpu_chain_all
+    bool gpu_stitch = false;  // --gpu_stitch[=max_link] (with --gpu_chain or --gpu_chain_all): a .stitched.maf file next to every .chain / .chains file (sa_stitch_chains)
+    uint32_t stitch_max_link = 0;  // sa_stitch_params.max_link; 0: the engine's default
+    bool stitch_min_set = false;
+    int stitch_min = INT32_MIN;    // --gpu_stitch_min=N: sa_stitch_params.min_link_score
     int gap_open = 400, gap_extend = 30;
     int xdrop = 910, hspthresh = 3000, ydrop = 9430, gappedthresh = -1;
     uint32_t wga_chunk = 250000, lastz_interval = 10000000, seq_block_size = 500000000;
@@ -262,12 +266,14 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
             std::string cname = base + (cfg.gpu_chain ? ".chain" : ".chains");
             f = fopen((cfg.outdir + "/" + cname).c_str(), "w");
             if (!f) die(7, "cant open file: %s", cname.c_str());
-            std::vector<uint32_t> idx;
+            std::vector<uint32_t> idx, cfirst(1, 0);  // cfirst: the chains' offsets into the members, for --gpu_stitch
             if (cfg.gpu_chain) {
                 sa_chain_member* mem = nullptr;
                 const size_t nm = sa_chain_hsps(v.data(), v.size(), group.data(), &cp, &mem, nullptr, nullptr);
                 idx.resize(nm);
                 for (size_t k = 0; k < nm; k++) { emit(v[mem[k].hsp_index]); idx[k] = mem[k].hsp_index; }  // the order sa_chain_hsps returns, on both strands
+                for (size_t k = 1; k <= nm; k++)
+                    if (k == nm || mem[k].group != mem[k - 1].group) cfirst.push_back((uint32_t)k);  // one chain per group
                 sa_free_chain(mem, nullptr);
             } else {
                 sa_chain_record* ch = nullptr;
@@ -279,10 +285,44 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
                     fprintf(f, "#chain %zu group=%u score=%lld members=%u joined=%d\n", c, ch[c].group, (long long)ch[c].score, ch[c].n_members,
                             ch[c].joined >= 0 ? 1 : 0);
                     for (size_t k = ch[c].first_member; k < (size_t)ch[c].first_member + ch[c].n_members; k++) { emit(v[mem[k].hsp_index]); idx[k] = mem[k].hsp_index; }
+                    cfirst.push_back(ch[c].first_member + ch[c].n_members);  // the chains' members follow one another
                 }
                 sa_free_chain_all(ch, mem, nullptr, nullptr);
             }
             fclose(f);
+            if (cfg.gpu_stitch) {  // every chain as one alignment through its members, in --gpu_maf's block layout
+                sa_stitch_params sp = {cfg.gap_open, cfg.gap_extend, cfg.stitch_max_link, cfg.stitch_min};
+                sa_stitch_record* sr = nullptr;
+                uint32_t* sops = nullptr;
+                size_t n_sops = 0;
+                const size_t ns = sa_stitch_chains(v.data(), v.size(), idx.data(), cfirst.data(), cfirst.size() - 1, rev, buffer, &sp, &sr, &sops, &n_sops,
+                                                   nullptr, nullptr, nullptr);
+                std::string sname = base + ".stitched.maf";
+                FILE* sf = fopen((cfg.outdir + "/" + sname).c_str(), "w");
+                if (!sf) die(7, "cant open file: %s", sname.c_str());
+                const std::string& qbuf = rev ? Qrc : Q.buf;
+                const std::vector<uint32_t>& ql = rev ? rc_chr_len : Q.chr_len;
+                for (size_t k = 0; k < ns; k++) {  // the order sa_stitch_chains returns, on both strands, as the .chain files
+                    const sa_stitch_record& a = sr[k];
+                    size_t r0 = a.ref_start + r_block_start, q0 = a.query_start + q_block_start;
+                    size_t ri = chr_of(R.chr_start, r0), qi = chr_of(qs, q0);
+                    std::string ta, qa;
+                    size_t i = r0, j = q0;
+                    for (size_t x = a.op_offset; x < a.op_offset + a.n_ops; x++) {
+                        const size_t len = sops[x] >> 2, op = sops[x] & 3u;
+                        if (op == SA_GAPPED_OP_I) ta.append(len, '-');
+                        else { ta.append(R.buf, i, len); i += len; }
+                        if (op == SA_GAPPED_OP_D) qa.append(len, '-');
+                        else { qa.append(qbuf, j, len); j += len; }
+                    }
+                    fprintf(sf, "a score=%lld\n", (long long)a.score);
+                    fprintf(sf, "s %s %zu %u + %u %s\n", R.chr_name[ri].c_str(), r0 - R.chr_start[ri], a.ref_end - a.ref_start, R.chr_len[ri], ta.c_str());
+                    fprintf(sf, "s %s %zu %u %c %u %s\n\n", qn[qi].c_str(), q0 - qs[qi], a.query_end - a.query_start, rev ? '-' : '+', ql[qi],
+                            qa.c_str());
+                }
+                fclose(sf);
+                sa_free_stitch(sr, sops, nullptr);
+            }
             std::sort(idx.begin(), idx.end());  // an HSP is a member of one chain at most: no duplicates
             kept.reserve(idx.size());
             for (uint32_t i : idx) kept.push_back(v[i]);
@@ -380,7 +420,11 @@ static void usage() {
             "  --gpu_chain_all[=diag,anti] (instead of --gpu_chain: a .chains file next to each .segments file with ALL collinear chains of\n"
             "      every pair, peeled best first, each under a line '#chain k group=g score=s members=m joined=0|1'; takes --gpu_chain_gap and\n"
             "      the same limit; --gpu_gapped then extends the HSPs of the chains kept)\n"
-            "  --gpu_chain_min=N (with --gpu_chain_all: chains that score less than N are not kept; default 0)\n");
+            "  --gpu_chain_min=N (with --gpu_chain_all: chains that score less than N are not kept; default 0)\n"
+            "  --gpu_stitch[=max_link] (with --gpu_chain or --gpu_chain_all: a .stitched.maf file next to each .chain / .chains file with every\n"
+            "      chain as one alignment through all its members, the stretch between two members aligned globally with --gap=O,E; a chain\n"
+            "      is cut where a side of that stretch exceeds max_link (default and at most 2048) or holds a record boundary)\n"
+            "  --gpu_stitch_min=N (with --gpu_stitch: a chain is also cut at a stretch whose alignment scores less than N)\n");
 }
 
 int main(int argc, char** argv) {
@@ -447,6 +491,21 @@ int main(int argc, char** argv) {
             if (endp == v.c_str() || *endp || gap < 0 || gap > 0xffffffffll) { fprintf(stderr, "bad --gpu_chain_gap=%s (0 .. 4294967295; 0: unlimited)\n", v.c_str()); return 1; }
             cfg.chain_gap = (uint32_t)gap;
         }
+        else if (!strcmp(a, "--gpu_stitch")) cfg.gpu_stitch = true;
+        else if (opt(a, "--gpu_stitch", v)) {
+            char* endp = nullptr;
+            const long long ml = strtoll(v.c_str(), &endp, 10);
+            if (endp == v.c_str() || *endp || ml < 1 || ml > 2048) { fprintf(stderr, "bad --gpu_stitch=%s (max_link: 1 .. 2048)\n", v.c_str()); return 1; }
+            cfg.gpu_stitch = true;
+            cfg.stitch_max_link = (uint32_t)ml;
+        }
+        else if (opt(a, "--gpu_stitch_min", v)) {
+            char* endp = nullptr;
+            const long long ms = strtoll(v.c_str(), &endp, 10);
+            if (endp == v.c_str() || *endp || ms < INT32_MIN || ms > INT32_MAX) { fprintf(stderr, "bad --gpu_stitch_min=%s (a 32-bit integer)\n", v.c_str()); return 1; }
+            cfg.stitch_min = (int)ms;
+            cfg.stitch_min_set = true;
+        }
         else if (opt(a, "--gap", v)) {
             if (sscanf(v.c_str(), "%d,%d", &cfg.gap_open, &cfg.gap_extend) != 2) { fprintf(stderr, "bad --gap=%s\n", v.c_str()); return 1; }
         }
@@ -459,6 +518,8 @@ int main(int argc, char** argv) {
     }
     if (cfg.gpu_chain && cfg.gpu_chain_all) { fprintf(stderr, "--gpu_chain and --gpu_chain_all exclude each other\n"); return 1; }
     if (cfg.chain_min_set && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_chain_min needs --gpu_chain_all\n"); return 1; }
+    if (cfg.gpu_stitch && !cfg.gpu_chain && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_stitch needs --gpu_chain or --gpu_chain_all\n"); return 1; }
+    if (cfg.stitch_min_set && !cfg.gpu_stitch) { fprintf(stderr, "--gpu_stitch_min needs --gpu_stitch\n"); return 1; }
     cfg.target = pos[0];
     cfg.query = pos[1];
     if (pos.size() > 2) cfg.data_folder = pos[2];

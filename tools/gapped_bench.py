@@ -19,8 +19,13 @@ the chains before min_score, the chains, joined chains and members kept, the dou
 the gapped times on the kept chains' members beside those on the best chain and on all HSPs.  The chains, members and chain_of are
 checked against the numpy model (tests/hsp_chain_all_model.py) once per run, on the f and pred the --chain check computed.
 
+With --stitch [--stitch-max-link N] (which implies --chain-all) the kept chains go through sa_stitch_chains: the line then
+adds the links by sweep instance, the broken links by reason, the cells, member / sweep / walk ms, giga-cells per second of the sweep, the
+trace bytes and batches, and the target bases the stitched records span beside those the gapped alignments of the same members span.
+Records, ops and links are checked against the model (tests/stitch_model.py) once per run.
+
   python tools/gapped_bench.py [--workloads standin,lumpy] [--repeat 3] [--align] [--greedy] [--batches 1024,2048,...]
-                               [--pieces N] [--max-extent M] [--chain] [--chain-pen D,A] [--chain-all] [--chain-min N]
+                               [--pieces N] [--max-extent M] [--chain] [--chain-pen D,A] [--chain-all] [--chain-min N] [--stitch] [--stitch-max-link N]
 """
 import argparse
 import functools
@@ -158,7 +163,39 @@ def kept_fields(kept, repeat, align, greedy, prefix):
     return out
 
 
-def chain_all_fields(hsps, repeat, pen, min_score, dp, align, greedy):
+def stitch_fields(hsps, members, repeat, max_link):
+    """sa_stitch_chains on the kept chains, the run with the least sweep time, checked against the model."""
+    import stitch_model as S
+    mem, first = E.chain_csr(members)
+    best = None
+    for _ in range(repeat):
+        t0 = time.perf_counter()
+        r = E.StitchChains(hsps, mem, first, False, 0, max_link=max_link, links=True)
+        wall = (time.perf_counter() - t0) * 1e3
+        if best is None or r[3]["sweep_ms"] < best[0][3]["sweep_ms"]:
+            best = (r, wall)
+    (recs, ops, links, st), wall = best
+    t0 = time.perf_counter()
+    want = S.stitch(E.copy_ref_codes(), E.copy_query_codes(0, False), SUB, hsps, mem, first, max_link=max_link)
+    model_s = time.perf_counter() - t0
+    if not (np.array_equal(recs, want[0].astype(recs.dtype)) and np.array_equal(ops, want[1]) and np.array_equal(links, want[2].astype(links.dtype))):
+        raise SystemExit("sa_stitch_chains differs from the model")
+    swept = links[(links["flags"] & E.STITCH_LONG) == 0]
+    by_k = {str(k): int(np.count_nonzero([S.instance(int(d)) == k for d in swept["dt"]])) for k in S.INSTANCES}
+    grecs = E.GappedExtend(hsps[np.sort(members["hsp_index"])], False, 0, **KW)[0]
+    return {"stitch_max_link": int(max_link or S.MAX_LINK), "stitch_chains": int(first.size - 1), "stitch_members": int(mem.size),
+            "stitch_links": int(st["links"]), "stitch_swept": int(st["swept"]), "stitch_links_by_instance": by_k,
+            "stitch_long": int(st["long_links"]), "stitch_dead": int(st["dead_links"]), "stitch_low": int(st["low_links"]),
+            "stitch_records": int(st["records"]), "stitch_cells": int(st["cells"]), "stitch_member_ms": round(st["member_ms"], 3),
+            "stitch_sweep_ms": round(st["sweep_ms"], 3), "stitch_walk_ms": round(st["walk_ms"], 3), "stitch_call_ms": round(wall, 3),
+            "stitch_gcells_per_s": round(st["cells"] / (st["sweep_ms"] * 1e-3) / 1e9, 3) if st["sweep_ms"] > 0 else None,
+            "stitch_trace_bytes": int(st["trace_bytes"]), "stitch_batches": int(st["batches"]), "stitch_ops": int(ops.size),
+            "stitch_aligned_bases": int((recs["ref_end"].astype(np.int64) - recs["ref_start"]).sum()),
+            "stitch_gap_bases": int(recs["gap_bases"].sum()), "kept_gapped_aligned_bases": span(grecs)["aligned_bases"],
+            "kept_gapped_alignments": int(grecs.size), "stitch_model_checked": True, "stitch_model_s": round(model_s, 1)}
+
+
+def chain_all_fields(hsps, repeat, pen, min_score, dp, align, greedy, stitch=None):
     """sa_chain_hsps_all on the HSPs as one group, checked against the numpy model on the DP values `dp` that chain_fields checked, and
     the gapped entries on the kept chains' members."""
     import hsp_chain_all_model as A
@@ -180,10 +217,12 @@ def chain_all_fields(hsps, repeat, pen, min_score, dp, align, greedy):
            "peel_over_dp": round(st["peel_ms"] / st["kernel_ms"], 4) if st["kernel_ms"] > 0 else None, "all_call_ms": round(wall, 3),
            "all_model_checked": True}
     out.update(kept_fields(hsps[np.sort(members["hsp_index"])], repeat, align, greedy, "all_kept_"))
+    if stitch is not None:
+        out.update(stitch_fields(hsps, members, repeat, stitch))
     return out
 
 
-def chain_fields(hsps, repeat, pen, align, greedy, all_min=None):
+def chain_fields(hsps, repeat, pen, align, greedy, all_min=None, stitch=None):
     """sa_chain_hsps on the HSPs as one group, checked against the numpy model, and the gapped entries on the chain's members; with
     all_min also chain_all_fields."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -209,11 +248,11 @@ def chain_fields(hsps, repeat, pen, align, greedy, all_min=None):
            "chain_model_checked": True, "chain_model_s": round(model_s, 1)}
     out.update(kept_fields(kept, repeat, align, greedy, "kept_"))
     if all_min is not None:
-        out.update(chain_all_fields(hsps, repeat, pen, all_min, (f, pred), align, greedy))
+        out.update(chain_all_fields(hsps, repeat, pen, all_min, (f, pred), align, greedy, stitch))
     return out
 
 
-def run(name, repeat, align=False, greedy=False, with_sel=True, pieces=0, chain=None, chain_all_min=None):
+def run(name, repeat, align=False, greedy=False, with_sel=True, pieces=0, chain=None, chain_all_min=None, stitch=None):
     t, q = workload(name)
     if greedy or pieces:
         E.set_option("debug", 1)  # sa_gapped_align_greedy then prints its edge count, the continuation its pieces
@@ -261,7 +300,7 @@ def run(name, repeat, align=False, greedy=False, with_sel=True, pieces=0, chain=
     if greedy:
         extra.update(greedy_fields(hsps, repeat, with_sel))
     if chain is not None:
-        extra.update(chain_fields(hsps, repeat, chain, align, greedy, chain_all_min))
+        extra.update(chain_fields(hsps, repeat, chain, align, greedy, chain_all_min, stitch))
     E.ShutdownProcessor()
     if greedy or pieces:
         E.reset_option("debug")
@@ -287,13 +326,17 @@ def main():
     ap.add_argument("--chain-pen", default="0,0", help="with --chain: diag_pen,anti_pen")
     ap.add_argument("--chain-all", action="store_true", help="also peel the HSPs into all chains (sa_chain_hsps_all); implies --chain")
     ap.add_argument("--chain-min", type=int, default=0, help="with --chain-all: min_score")
+    ap.add_argument("--stitch", action="store_true", help="also stitch the kept chains (sa_stitch_chains); implies --chain-all")
+    ap.add_argument("--stitch-max-link", type=int, default=0, help="with --stitch: max_link (0: the default, 2048)")
     a = ap.parse_args()
+    a.chain_all = a.chain_all or a.stitch
     chain = tuple(int(x) for x in a.chain_pen.split(",")) if a.chain or a.chain_all else None
     if a.max_extent:
         KW["max_extent"] = a.max_extent
     for name in a.workloads.split(","):
         if not a.batches:
-            print(json.dumps(run(name, a.repeat, a.align, a.greedy, pieces=a.pieces, chain=chain, chain_all_min=a.chain_min if a.chain_all else None)), flush=True)
+            print(json.dumps(run(name, a.repeat, a.align, a.greedy, pieces=a.pieces, chain=chain, chain_all_min=a.chain_min if a.chain_all else None,
+                                 stitch=a.stitch_max_link if a.stitch else None)), flush=True)
             continue
         for b in a.batches.split(","):
             E.set_option("gapped_greedy_batch", int(b))
