@@ -344,6 +344,22 @@ size_t sa_extend_hits(const uint32_t* ref_query_pairs, size_t num_hits, int rev,
  * stable_sort / unique_copy in tests/test_gpu_thrust_order.py (hazard H3: unique_copy = head flags on adjacent INPUT pairs). */
 size_t sa_order_hsps(const sa_segment_pair* in, size_t n, int rm, int path, sa_segment_pair** out);
 
+/* Test entry: the ordering stage the way a call runs it, on `n` records of `nsegs` dedup scopes in one list; seg[i] < nsegs is the scope
+ * (reference iteration) of record i, and each scope gets the chain of sa_order_hsps on its own.
+ *   path 0  the per-segment LDS chain, one workgroup per segment: rm == 0, nsegs <= 512, and n <= 131072 unless count_on_device.
+ *           threads / seg_max are what the options dedup_threads / dedup_seg_max hand to the kernel (0 = 1024 threads, 2048 records per
+ *           segment); count_on_device != 0 passes n through a device word, as the speculative launch of a call does.  The raw slots
+ *           are downloaded and their gaps closed by the host code a call uses.  If the kernel refuses (a segment above seg_max, or a
+ *           device-side count above 131072) *refused = 1 and nothing is returned: there is no fallback, the caller decides.
+ *   path 1  the library-sort chain with the segment as the major key (rm: the repeat masker's chain), any n and nsegs.
+ * *out: the records ordered by segment, then in the chain's order; *out_seg: the segment of each (both malloc'ed, sa_free_segments);
+ * seg_counts[nsegs], the caller's: records kept per segment.  Returns the number of records kept.  Input no call would hand to a
+ * path -- path 0 with rm, with more than 512 segments or with a host-side count above 131072, a segment id >= nsegs -- ends the
+ * process with a message and exit code 1.  Held against tests/order_model.py in tests/test_gpu_order_regimes.py. */
+size_t sa_order_hsps_segs(const sa_segment_pair* in, const uint32_t* seg, size_t n, uint32_t nsegs, int rm, int path, uint32_t threads,
+                          uint32_t seg_max, int count_on_device, sa_segment_pair** out, uint32_t** out_seg, uint32_t* seg_counts,
+                          int* refused);
+
 /* ---- gapped extension of HSP anchors (additive) ------------------------------------------------
  *
  * The gapped stage the reference hands to LASTZ (src/segment_printer.cpp:96-113), done on the device with semantics of this

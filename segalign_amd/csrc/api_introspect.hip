@@ -123,4 +123,107 @@ size_t sa_order_hsps(const sa_segment_pair* in, size_t n, int rm, int path, sa_s
     return m;
 }
 
+// The ordering stage the way a call runs it: records of SEVERAL dedup scopes (`seg[i]` < nsegs, the reference iteration of record i) in
+// one list.  path 0: launch_dedup_seg with one workgroup per segment, `threads` and `seg_max` as the options dedup_threads /
+// dedup_seg_max hand them over, the record count as a launch argument or (count_on_device) through a device word as the speculative
+// launch of saf_core passes it; the raw slots are downloaded and their gaps closed by saf_core's own close_seg_gaps.  A refusal of the
+// kernel (a segment above seg_max, a device-side count above its total) sets *refused and returns nothing: the caller decides what to
+// do next, as saf_core does.  path 1: the library chain with the segment as the major key, plain or rm, stripped with out_seg.
+// Test entry (tests/test_gpu_order_regimes.py): own buffers, device 0, default stream.  seg_counts: nsegs words.
+size_t sa_order_hsps_segs(const sa_segment_pair* in, const uint32_t* seg, size_t n, uint32_t nsegs, int rm, int path, uint32_t threads,
+                          uint32_t seg_max, int count_on_device, sa_segment_pair** out, uint32_t** out_seg, uint32_t* seg_counts,
+                          int* refused) {
+    *out = nullptr;
+    *out_seg = nullptr;
+    *refused = 0;
+    if (g_ndev <= 0) {
+        fprintf(stderr, "Error: sa_order_hsps_segs before InitializeInterface\n");
+        exit(11);
+    }
+    for (uint32_t g = 0; g < nsegs; g++) seg_counts[g] = 0;
+    if (n > 0x7FFFFFFFull || (path == 0 && (rm || nsegs > dedup_small_max_segs() || (!count_on_device && n > dedup_seg_max_total())))) {
+        fprintf(stderr, "Error: sa_order_hsps_segs: %zu records in %u segments (rm %d) do not fit path %d\n", n, nsegs, rm, path);
+        exit(1);
+    }
+    for (size_t i = 0; i < n; i++)
+        if (seg[i] >= nsegs) {
+            fprintf(stderr, "Error: sa_order_hsps_segs: record %zu has segment %u of %u\n", i, seg[i], nsegs);
+            exit(1);
+        }
+    if (n == 0) return 0;
+    ctx_of(0);
+    std::vector<HspRec> h(n);
+    for (size_t i = 0; i < n; i++) { h[i].ref_start = in[i].ref_start; h[i].query_start = in[i].query_start; h[i].len = in[i].len; h[i].score = in[i].score; h[i].seg = seg[i]; }
+    HspRec *a = nullptr, *b = nullptr;
+    uint4* o16 = nullptr;
+    uint32_t *misc = nullptr, *oseg = nullptr;  // misc: [0] counter, [1] the record count for the kernel | seg_info
+    void *stmp = nullptr, *utmp = nullptr;
+    const size_t sbytes = sort_temp_bytes(n), ubytes = unique_temp_bytes((uint32_t)n), iwords = dedup_seg_info_words() + 4;
+    check_memcpy(hipMalloc((void**)&a, n * sizeof(HspRec)), "order segs: records");
+    check_memcpy(hipMalloc((void**)&b, n * sizeof(HspRec)), "order segs: records");
+    check_memcpy(hipMalloc((void**)&o16, n * sizeof(uint4)), "order segs: output");
+    check_memcpy(hipMalloc((void**)&oseg, n * sizeof(uint32_t)), "order segs: output segments");
+    check_memcpy(hipMalloc((void**)&misc, iwords * sizeof(uint32_t)), "order segs: counters");
+    check_memcpy(hipMalloc(&stmp, sbytes), "order segs: sort temp");
+    check_memcpy(hipMalloc(&utmp, ubytes), "order segs: unique temp");
+    check_memcpy(hipMemcpy(a, h.data(), n * sizeof(HspRec), hipMemcpyHostToDevice), "order segs: upload");
+    check_memcpy(hipMemset(misc, 0, iwords * sizeof(uint32_t)), "order segs: counters");  // (the segment-info words must be zero on entry)
+    hipStream_t st = 0;
+    size_t m = 0;
+    sa_segment_pair* res = (sa_segment_pair*)malloc(n * sizeof(sa_segment_pair));
+    uint32_t* rseg = (uint32_t*)malloc(n * sizeof(uint32_t));
+    auto count = [&]() { uint32_t c = 0; check_memcpy(hipMemcpy(&c, misc, sizeof(c), hipMemcpyDeviceToHost), "order segs: count"); return (size_t)c; };
+    if (path == 0) {
+        uint32_t* info = misc + 4;
+        if (count_on_device) {
+            const uint32_t n32 = (uint32_t)n;
+            check_memcpy(hipMemcpy(misc + 1, &n32, sizeof(n32), hipMemcpyHostToDevice), "order segs: device count");
+            launch_dedup_seg(a, 0, misc + 1, nsegs, o16, info, threads, seg_max, st);
+        } else {
+            launch_dedup_seg(a, (uint32_t)n, nullptr, nsegs, o16, info, threads, seg_max, st);
+        }
+        check_launch("order segs: dedup seg");
+        std::vector<uint32_t> hi(dedup_seg_info_words());
+        check_memcpy(hipMemcpy(hi.data(), info, hi.size() * sizeof(uint32_t), hipMemcpyDeviceToHost), "order segs: segment info");
+        if (hi[hi.size() - 1] != 0) {
+            *refused = 1;
+        } else {
+            check_memcpy(hipMemcpy(res, o16, n * sizeof(sa_segment_pair), hipMemcpyDeviceToHost), "order segs: download");  // the raw slots
+            m = close_seg_gaps(res, rseg, hi.data(), nsegs);
+        }
+    } else {
+        if (!rm) {
+            launch_sort(a, b, n, ORDER_DIAG, stmp, sbytes, st);
+            launch_unique(b, a, (uint32_t)n, 0, misc, utmp, st);
+            m = count();
+            launch_sort(a, b, m, ORDER_LASTZ, stmp, sbytes, st);
+        } else {
+            launch_sort(a, b, n, ORDER_RM_FIRST, stmp, sbytes, st);
+            launch_unique(b, a, (uint32_t)n, 1, misc, utmp, st);
+            const size_t m1 = count();
+            launch_sort(a, b, m1, ORDER_RM_DIAG, stmp, sbytes, st);
+            launch_unique(b, a, (uint32_t)m1, 0, misc, utmp, st);
+            m = count();
+            launch_sort(a, b, m, ORDER_RM_FINAL, stmp, sbytes, st);
+        }
+        launch_strip(b, (uint32_t)m, o16, oseg, st);
+        check_launch("order segs: sort chain");
+        if (m) {
+            check_memcpy(hipMemcpy(res, o16, m * sizeof(sa_segment_pair), hipMemcpyDeviceToHost), "order segs: download");
+            check_memcpy(hipMemcpy(rseg, oseg, m * sizeof(uint32_t), hipMemcpyDeviceToHost), "order segs: segments");
+        }
+    }
+    (void)hipFree(a); (void)hipFree(b); (void)hipFree(o16); (void)hipFree(oseg); (void)hipFree(misc); (void)hipFree(stmp); (void)hipFree(utmp);
+    if (*refused) {
+        free(res);
+        free(rseg);
+        return 0;
+    }
+    for (size_t i = 0; i < m; i++)
+        if (rseg[i] < nsegs) seg_counts[rseg[i]]++;
+    *out = res;
+    *out_seg = rseg;
+    return m;
+}
+
 }  // extern "C"

@@ -4,6 +4,21 @@
 
 namespace sa {
 
+// The per-segment LDS chain (dedup_seg_kernel) leaves segment g's seg_info[g] records at slot seg_info[S + g] of `recs`, the offset of the
+// segment's INPUT records: close the gaps the unique step left, front to back (a segment never moves right), and note the segment of
+// every record in seg_of.  -> records kept
+size_t close_seg_gaps(sa_segment_pair* recs, uint32_t* seg_of, const uint32_t* seg_info, uint32_t nsegs) {
+    const uint32_t S = dedup_small_max_segs();
+    size_t pos = 0;
+    for (uint32_t g = 0; g < nsegs; g++) {
+        const uint32_t m2 = seg_info[g], off = seg_info[S + g];
+        if (m2 && pos != off) memmove(recs + pos, recs + off, (size_t)m2 * sizeof(sa_segment_pair));
+        for (uint32_t i = 0; i < m2; i++) seg_of[pos + i] = g;
+        pos += m2;
+    }
+    return pos;
+}
+
 size_t saf_core(DevCtx* dc, Slot* sl, uint32_t num_seeds, const CoreArgs& ca, sa_segment_pair** out) {
     hipStream_t st = sl->stream;
     memset(&t_stats, 0, sizeof(t_stats));
@@ -405,15 +420,7 @@ size_t saf_core(DevCtx* dc, Slot* sl, uint32_t num_seeds, const CoreArgs& ca, sa
                                                 hipMemcpyDeviceToHost, st), "hsp_output");
                     check_sync(st, "hsp_output");
                 }
-                const uint32_t S = dedup_small_max_segs();
-                size_t pos = 0;
-                for (uint32_t g = 0; g < (uint32_t)segs.size(); g++) {  // close the gaps the unique step left
-                    const uint32_t m2 = sl->h_seg_info[g], off = sl->h_seg_info[S + g];
-                    if (m2 && pos != off) memmove(sl->h_out + pos, sl->h_out + off, (size_t)m2 * sizeof(sa_segment_pair));
-                    for (uint32_t i = 0; i < m2; i++) sl->h_seg[pos + i] = g;
-                    pos += m2;
-                }
-                n_final = (uint32_t)pos;
+                n_final = (uint32_t)close_seg_gaps(sl->h_out, sl->h_seg, sl->h_seg_info, (uint32_t)segs.size());
                 have_seg = true;
             } else if (survivors > 0 && ca.raw_hits) {  // the extension stage's own output, unordered
                 sl->out16.ensure(survivors, "out16");
@@ -445,15 +452,7 @@ size_t saf_core(DevCtx* dc, Slot* sl, uint32_t num_seeds, const CoreArgs& ca, sa
                                                 hipMemcpyDeviceToHost, st), "hsp_output");  // :788
                     check_sync(st, "hsp_output");
                     if (sl->h_seg_info[words - 1] == 0) {  // (else a segment was too large for LDS: library sorts below)
-                        const uint32_t S = dedup_small_max_segs();
-                        size_t pos = 0;
-                        for (uint32_t g = 0; g < (uint32_t)segs.size(); g++) {  // close the gaps the unique step left
-                            const uint32_t m2 = sl->h_seg_info[g], off = sl->h_seg_info[S + g];
-                            if (m2 && pos != off) memmove(sl->h_out + pos, sl->h_out + off, (size_t)m2 * sizeof(sa_segment_pair));
-                            for (uint32_t i = 0; i < m2; i++) sl->h_seg[pos + i] = g;
-                            pos += m2;
-                        }
-                        n_final = (uint32_t)pos;
+                        n_final = (uint32_t)close_seg_gaps(sl->h_out, sl->h_seg, sl->h_seg_info, (uint32_t)segs.size());
                         have_seg = true;
                         done = true;
                     }

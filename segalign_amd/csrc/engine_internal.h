@@ -565,6 +565,8 @@ struct CoreArgs {
 };
 
 size_t saf_core(DevCtx* dc, Slot* sl, uint32_t num_seeds, const CoreArgs& ca, sa_segment_pair** out);
+// host step after launch_dedup_seg: closes the gaps between the segments' slot ranges (seg_info as the kernel wrote it) -> records kept
+size_t close_seg_gaps(sa_segment_pair* recs, uint32_t* seg_of, const uint32_t* seg_info, uint32_t nsegs);
 
 // ---- the front of a call (front.hip) ----
 void upload_seeds(Slot* sl, const uint64_t* seeds, size_t n);

@@ -36,6 +36,7 @@ C_ABI_SYMBOLS = [
     "sa_copy_query_codes", "sa_get_query_len", "sa_device_make_seeds", "sa_version",
     "sa_rm_mask_interval", "sa_rm_coverage_intervals", "sa_free_intervals", "sa_get_filter_mode",
     "sa_seed_interval", "sa_seed_and_filter_chunks", "sa_max_chunks_per_call", "sa_get_chunks_per_call", "sa_extend_hits", "sa_order_hsps",
+    "sa_order_hsps_segs",
     "sa_get_lookup_mode", "sa_get_neighbourhood_entries",
     "sa_seed_calls", "sa_count_call_hits", "sa_count_chunk_hits", "sa_get_wga_chunk", "sa_release_arena", "sa_set_option", "sa_reset_option", "sa_get_option", "sa_option_count", "sa_option_name", "sa_get_audit",
     "sa_gapped_extend", "sa_free_gapped", "sa_gapped_align", "sa_free_gapped_align", "sa_gapped_align_greedy",
@@ -190,6 +191,9 @@ def lib():
     L.sa_device_make_seeds.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t]
     L.sa_order_hsps.restype = C.c_size_t
     L.sa_order_hsps.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.sa_order_hsps_segs.restype = C.c_size_t
+    L.sa_order_hsps_segs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int,
+                                     C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_int)]
     L.sa_extend_hits.restype = C.c_size_t
     L.sa_extend_hits.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]
     L.sa_get_neighbourhood_entries.restype = C.c_uint64
@@ -399,6 +403,26 @@ def OrderHsps(records, rm=False, path=1):
     res = np.frombuffer((C.c_char * (n * SEG_DTYPE.itemsize)).from_address(out.value), dtype=SEG_DTYPE).copy() if n else np.zeros(0, dtype=SEG_DTYPE)
     lib().sa_free_segments(out)
     return res
+
+
+def OrderHspsSegs(records, seg, nsegs, rm=False, path=1, threads=0, seg_max=0, count_on_device=False):
+    """The ordering stage on records of `nsegs` dedup scopes (seg[i] < nsegs) the way a call runs it (sa_order_hsps_segs; test entry).
+    -> (records, the segment of each, records kept per segment, refused).  A refused path-0 call returns no records."""
+    h = np.ascontiguousarray(records, dtype=SEG_DTYPE)
+    sg = np.ascontiguousarray(seg, dtype=np.uint32)
+    assert sg.shape == h.shape
+    counts = np.zeros(int(nsegs), dtype=np.uint32)
+    out, oseg, refused = C.c_void_p(), C.c_void_p(), C.c_int(0)
+    n = lib().sa_order_hsps_segs(h.ctypes.data if h.size else None, sg.ctypes.data if sg.size else None, h.size, int(nsegs), int(bool(rm)),
+                                 int(path), int(threads), int(seg_max), int(bool(count_on_device)), C.byref(out), C.byref(oseg),
+                                 counts.ctypes.data if counts.size else None, C.byref(refused))
+    res, rseg = np.zeros(0, dtype=SEG_DTYPE), np.zeros(0, dtype=np.uint32)
+    if out.value and n:
+        res = np.frombuffer((C.c_char * (n * SEG_DTYPE.itemsize)).from_address(out.value), dtype=SEG_DTYPE).copy()
+        rseg = np.frombuffer((C.c_char * (n * 4)).from_address(oseg.value), dtype=np.uint32).copy()
+    lib().sa_free_segments(out)
+    lib().sa_free_segments(oseg)
+    return res, rseg, counts, bool(refused.value)
 
 
 def ExtendHits(hits, rev, buffer):
