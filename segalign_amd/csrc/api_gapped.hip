@@ -6,8 +6,7 @@
 #include <functional>
 #include <unordered_map>
 
-#include "engine_internal.h"
-#include "gapped.h"
+#include "post_host.h"
 
 using namespace sa;
 
@@ -45,26 +44,17 @@ Params resolve(const sa_gapped_params* p) {
 // One entry's checks and parameters, and for n > 0 its slot, query strand and the kernel arguments every launch shares.  release(), at
 // the latest on leaving scope, flushes the slot's profile and gives the slot back.
 struct Frame {
+    const char* who;
     Params P;
     Slot* sl = nullptr;
     GappedArgs a;  // hsps, num_tasks and out are set per launch
-    Frame(const char* who, size_t n, int rev, uint32_t buffer, const sa_gapped_params* p) {
+    Frame(const char* name, size_t n, int rev, uint32_t buffer, const sa_gapped_params* p) : who(name) {
         require_proc(who, buffer);
         P = resolve(p);
         memset(&a, 0, sizeof(a));
         if (n == 0) return;
         sl = acquire_slot();
-        const DevCtx* dc = sl->ctx;
-        const SeqBuf& q = rev ? dc->query_rc[buffer] : dc->query[buffer];
-        if (!dc->ref.codes || !q.codes) {
-            fprintf(stderr, "Error: %s needs a resident target block and query buffer %u\n", who, buffer);
-            exit(1);
-        }
-        a.ref = dc->ref.codes;
-        a.ref_len = dc->ref.len;
-        a.query = q.codes;
-        a.query_len = q.len;
-        a.sub_mat = dc->d_sub_mat;
+        resident_block(who, sl, rev, buffer, a);
         a.gap_open = P.gap_open;
         a.gap_extend = P.gap_extend;
         a.ydrop = P.ydrop;
@@ -80,61 +70,6 @@ struct Frame {
         sl = nullptr;
     }
 };
-
-// Device time between N events on one stream: ms(i, j) once the stream has passed mark j (where the caller synchronises, or wait()).
-template <int N>
-struct Timer {
-    hipStream_t s;
-    hipEvent_t e[N];
-    explicit Timer(hipStream_t st) : s(st) {
-        for (hipEvent_t& x : e) ok(hipEventCreate(&x), "hipEventCreate");
-    }
-    ~Timer() {
-        for (hipEvent_t x : e) hipEventDestroy(x);
-    }
-    void mark(int i) { ok(hipEventRecord(e[i], s), "hipEventRecord"); }
-    double ms(int i, int j) {
-        float x = 0;
-        ok(hipEventElapsedTime(&x, e[i], e[j]), "hipEventElapsedTime");
-        return x;
-    }
-    double wait(int i, int j) {
-        ok(hipEventSynchronize(e[j]), "hipEventSynchronize");
-        return ms(i, j);
-    }
-    static void ok(hipError_t r, const char* what) {
-        if (r != hipSuccess) die(15, what, "gapped timing", r);
-    }
-};
-
-// Launches profiled as one scope and checked, both under name.
-template <typename F>
-void launch(Slot* sl, const char* name, F&& launches) {
-    ProfScope ps(sl, name);
-    launches();
-    check_launch(name);
-}
-
-// 256-byte-aligned sub-buffers of buf: layout(c) calls c.take(pointer, count) in order, once to size buf and once to set the pointers.
-struct Carve {
-    uint8_t* base;
-    size_t end = 0;
-    template <typename T>
-    Carve& take(T*& p, size_t n) {
-        const size_t at = (end + 255) & ~(size_t)255;
-        end = at + n * sizeof(T);
-        p = base ? (T*)(base + at) : nullptr;
-        return *this;
-    }
-};
-template <typename F>
-void carve(DevBuf<uint8_t>& buf, const char* tag, F&& layout) {
-    Carve size{nullptr};
-    layout(size);
-    buf.ensure(size.end, tag);
-    Carve c{buf.p};
-    layout(c);
-}
 
 // An HSP's anchor point (t, q), and the key of a point in the cover index: diag << 32 | t with diag = t - q + query_len.
 struct Point {
@@ -164,7 +99,7 @@ std::vector<GappedSide> extend_sides(Frame& f, const sa_segment_pair* hsps, size
     GappedSide* d_side;
     carve(sl->gapped, "gapped", [&](Carve& c) { c.take(d_hsps, batch).take(d_side, 2 * batch); });
     std::vector<GappedSide> side(2 * n);
-    Timer<2> tm(sl->stream);
+    Timer<2> tm(sl->stream, "gapped timing");
     GappedArgs a = f.a;
     a.hsps = d_hsps;
     a.out = d_side;
@@ -215,7 +150,7 @@ void continue_sides(Frame& f, const sa_segment_pair* hsps, Sides& S, sa_gapped_s
     SideTask* d_tasks;
     GappedSide* d_side;
     carve(sl->gapped, "gapped", [&](Carve& c) { c.take(d_tasks, batch).take(d_side, batch); });
-    Timer<2> tm(sl->stream);
+    Timer<2> tm(sl->stream, "gapped timing");
     std::vector<SideTask> tasks;
     std::vector<GappedSide> res;
     size_t pieces = 0, rounds = 0;
@@ -360,67 +295,41 @@ using TraceHook = std::function<void(const TraceTask*, const TraceOut*, const ui
 void trace_sides(Frame& f, Traces& tr, sa_gapped_align_stats& st, const TraceHook& hook = nullptr) {
     Slot* sl = f.sl;
     const std::vector<TraceTask>& tasks = tr.tasks;
-    const size_t budget = (size_t)g_gapped_trace_mb << 20;
     const size_t nt = tasks.size();
     tr.res.resize(nt);
     tr.off.resize(nt);
-    Timer<3> tm(sl->stream);
-    std::vector<TraceTask> bt;
+    Timer<3> tm(sl->stream, "gapped timing");
+    TraceBatch bt;
     std::vector<uint32_t> bops;
     for (size_t b = 0; b < nt;) {
-        // the batch: tasks [b, e), their trace areas within the budget (a larger side alone)
-        size_t e = b, trace = 0, nops = 0;
-        bt.clear();
-        while (e < nt) {
-            const size_t tb = gapped_trace_bytes(f.P.max_band, tasks[e].dstar);
-            if (e > b && trace + tb > budget) break;
-            TraceTask t = tasks[e];
-            t.trace_off = trace;
-            t.ops_off = nops;
-            bt.push_back(t);
-            trace += tb;
-            nops += (size_t)t.dstar;
-            e++;
-        }
-        const size_t m = e - b;
+        const size_t e = bt.pack(tasks, b, f.P.max_band), m = e - b;  // the batch: tasks [b, e)
         TraceTask* d_tasks;
         TraceOut* d_out;
         uint32_t* d_ops;
         uint8_t* d_area;
-        carve(sl->gapped_trace, "gapped trace", [&](Carve& c) { c.take(d_tasks, m).take(d_out, m).take(d_ops, nops).take(d_area, trace); });
-        check_memcpy(hipMemcpyAsync(d_tasks, bt.data(), m * sizeof(TraceTask), hipMemcpyHostToDevice, sl->stream), "gapped trace tasks");
+        carve(sl->gapped_trace, "gapped trace", [&](Carve& c) { c.take(d_tasks, m).take(d_out, m).take(d_ops, bt.nops).take(d_area, bt.trace); });
+        check_memcpy(hipMemcpyAsync(d_tasks, bt.tasks.data(), m * sizeof(TraceTask), hipMemcpyHostToDevice, sl->stream), "gapped trace tasks");
         tm.mark(0);
         launch(sl, "gapped_trace", [&] { launch_gapped_trace(f.a, d_tasks, (uint32_t)m, d_area, sl->stream); });
         tm.mark(1);
         launch(sl, "gapped_walk", [&] { launch_gapped_walk(f.a, d_tasks, (uint32_t)m, d_area, d_ops, d_out, sl->stream); });
         tm.mark(2);
-        bops.resize(nops);
+        bops.resize(bt.nops);
         check_memcpy(hipMemcpyAsync(tr.res.data() + b, d_out, m * sizeof(TraceOut), hipMemcpyDeviceToHost, sl->stream), "gapped walk results");
-        check_memcpy(hipMemcpyAsync(bops.data(), d_ops, nops * sizeof(uint32_t), hipMemcpyDeviceToHost, sl->stream), "gapped ops");
+        check_memcpy(hipMemcpyAsync(bops.data(), d_ops, bt.nops * sizeof(uint32_t), hipMemcpyDeviceToHost, sl->stream), "gapped ops");
         check_sync(sl->stream, "gapped_align");
         st.trace_ms += tm.ms(0, 1);
         st.walk_ms += tm.ms(1, 2);
-        st.trace_bytes += trace;
+        st.trace_bytes += bt.trace;
         st.trace_batches++;
-        for (size_t k = 0; k < m; k++) {
-            const TraceOut& r = tr.res[b + k];
-            if (r.err || r.n_runs > (uint32_t)bt[k].dstar) {
-                fprintf(stderr, "Error: GappedAlign: the path walk left the traced cells (side %zu, code %u)\n", b + k, r.err);
+        for (size_t k = 0; k < m; k++)
+            if (!take_runs(bt.tasks[k], tr.res[b + k], bops, tr.runs, tr.off[b + k])) {
+                fprintf(stderr, "Error: GappedAlign: the path walk left the traced cells (side %zu, code %u)\n", b + k, tr.res[b + k].err);
                 exit(1);
             }
-            tr.off[b + k] = tr.runs.size();
-            tr.runs.insert(tr.runs.end(), bops.begin() + bt[k].ops_off, bops.begin() + bt[k].ops_off + r.n_runs);
-        }
         if (hook) hook(d_tasks, d_out, d_ops, b, m);
         b = e;
     }
-}
-
-template <typename T>
-T* malloc_copy(const std::vector<T>& v) {  // nullptr for none
-    T* p = v.empty() ? nullptr : (T*)malloc(v.size() * sizeof(T));
-    if (p) memcpy(p, v.data(), v.size() * sizeof(T));
-    return p;
 }
 
 // An entry's records, their paths and the paths' ops.
@@ -471,13 +380,13 @@ struct Output {
     }
     // The stats and malloc-ed copies, paths and ops unless paths is nullptr (sa_gapped_extend); returns the number of records.
     template <typename Stats>
-    size_t hand_out(const Stats& st, Stats* stats, sa_gapped_alignment** out, sa_gapped_path** paths = nullptr, uint32_t** ops_out = nullptr,
-                    size_t* n_ops = nullptr) {
+    size_t hand_out(const char* who, const Stats& st, Stats* stats, sa_gapped_alignment** out, sa_gapped_path** paths = nullptr,
+                    uint32_t** ops_out = nullptr, size_t* n_ops = nullptr) {
         if (stats) *stats = st;
-        *out = malloc_copy(rec);
+        *out = malloc_copy(rec, who);
         if (paths) {
-            *paths = malloc_copy(pa);
-            *ops_out = malloc_copy(ops);
+            *paths = malloc_copy(pa, who);
+            *ops_out = malloc_copy(ops, who);
             *n_ops = ops.size();
         }
         return rec.size();
@@ -505,7 +414,7 @@ struct CoverIndex {
     uint32_t R = 0;
     int cur = 0;
     uint64_t edges = 0, max_edges = 0, passes = 0;
-    explicit CoverIndex(Slot* s) : sl(s), tm(s->stream) {}
+    explicit CoverIndex(Slot* s) : sl(s), tm(s->stream, "gapped timing") {}
     template <typename F>
     void group(const char* name, F&& launches) {
         tm.mark(0);
@@ -708,7 +617,7 @@ size_t sa_gapped_extend(const sa_segment_pair* hsps, size_t n, int rev, uint32_t
         f.release();
         o.rec = make_records(hsps, n, S.side, f.P, raw, st);
     }
-    return o.hand_out(st, stats, out);
+    return o.hand_out(f.who, st, stats, out);
 }
 
 void sa_free_gapped(sa_gapped_alignment* p) { free(p); }
@@ -729,7 +638,7 @@ size_t sa_gapped_align(const sa_segment_pair* hsps, size_t n, int rev, uint32_t 
         o.ops.reserve(tr.runs.size());
         for (size_t k = 0; k < o.rec.size(); k++) o.add_path(tr, k);
     }
-    return o.hand_out(st, stats, out, paths, ops, n_ops);
+    return o.hand_out(f.who, st, stats, out, paths, ops, n_ops);
 }
 
 void sa_free_gapped_align(sa_gapped_alignment* out, sa_gapped_path* paths, uint32_t* ops) {
@@ -746,7 +655,7 @@ size_t sa_gapped_align_greedy(const sa_segment_pair* hsps, size_t n, int rev, ui
     Frame f("GappedAlignGreedy", n, rev, buffer, p);
     sa_gapped_greedy_stats st = {};
     Output o;  // the accepted records, in acceptance order until sorted
-    if (n == 0) return o.hand_out(st, stats, out, paths, ops, n_ops);
+    if (n == 0) return o.hand_out(f.who, st, stats, out, paths, ops, n_ops);
     std::vector<uint32_t> pi(n);  // the priority order
     for (size_t k = 0; k < n; k++) pi[k] = (uint32_t)k;
     std::sort(pi.begin(), pi.end(), [&](uint32_t x, uint32_t y) { return hsps[x].score != hsps[y].score ? hsps[x].score > hsps[y].score : x < y; });
@@ -800,7 +709,7 @@ size_t sa_gapped_align_greedy(const sa_segment_pair* hsps, size_t n, int rev, ui
                 (unsigned long long)st.priority_batches, (unsigned long long)ix.passes, (unsigned long long)ix.edges, (unsigned long long)ix.max_edges);
     st.align.extend.returned = o.rec.size();  // the accepted records, not the sum of the batches' extended ones
     o.sort();
-    return o.hand_out(st, stats, out, paths, ops, n_ops);
+    return o.hand_out(f.who, st, stats, out, paths, ops, n_ops);
 }
 
 }  // extern "C"

@@ -3,8 +3,7 @@
 // The host side: checks, the slot, rank (two stable radix sorts) and the tile loop (hspchain.hip: cross, resolve), shared by both; then
 // sa_chain_hsps's finish (group starts, ends, members, nodes) or the peel (hsppeel.hip: subtree minimum, chain order, members), and the
 // counts the kernels' work is reported by.
-#include "engine_internal.h"
-#include "gapped.h"  // cover.hip's rocPRIM wrappers: cover_sort_anchors, cover_scan_offsets
+#include "post_host.h"  // and through it gapped.h: cover.hip's rocPRIM wrappers cover_sort_anchors, cover_scan_offsets
 #include "hspchain.h"
 #include "hsppeel.h"
 
@@ -17,42 +16,8 @@ void bad(const char* what, long long v) {
     exit(1);
 }
 
-struct Take {  // 256-byte-aligned pieces of one buffer: sized with base == nullptr, then laid out
-    uint8_t* base;
-    size_t end = 0;
-    template <typename T>
-    void operator()(T*& p, size_t n) {
-        const size_t at = (end + 255) & ~(size_t)255;
-        end = at + n * sizeof(T);
-        p = base ? (T*)(base + at) : nullptr;
-    }
-};
-
-struct Events {  // pairs of events on the slot's stream: span k runs from mark(2 k) to mark(2 k + 1)
-    static constexpr int MAX = 10;
-    hipStream_t s;
-    int n;  // events in use: 8 for sa_chain_hsps, 10 for sa_chain_hsps_all
-    hipEvent_t e[MAX];
-    Events(hipStream_t st, int count) : s(st), n(count) {
-        for (int i = 0; i < n; i++) ok(hipEventCreate(&e[i]));
-    }
-    ~Events() {
-        for (int i = 0; i < n; i++) hipEventDestroy(e[i]);
-    }
-    void mark(int i) { ok(hipEventRecord(e[i], s)); }
-    double total(int first, int spans) {  // spans first .. first + spans - 1, after the stream has been synchronised
-        double ms = 0;
-        for (int k = 2 * first; k < 2 * (first + spans); k += 2) {
-            float x = 0;
-            ok(hipEventElapsedTime(&x, e[k], e[k + 1]));
-            ms += x;
-        }
-        return ms;
-    }
-    static void ok(hipError_t r) {
-        if (r != hipSuccess) die(15, "event", "hsp chain timing", r);
-    }
-};
+// The events of one call: marks 0-1 span the rank step and 2-3 the DP (rank_and_dp), 4-7 the finish or the peel.
+using ChainTimer = Timer<8>;
 
 // What the rank step and the DP leave on the slot's stream, for the finish of sa_chain_hsps and the peel of sa_chain_hsps_all.
 struct ChainDp {
@@ -72,7 +37,7 @@ struct ChainDp {
 
 // The slot's buffers, the upload, rank and the DP (spans 0 and 1 of ev) for n > 0 HSPs on the slot d.sl.  Returns with the stream
 // synchronised, G known and st's pair_evals and tile_steps counted.
-void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, uint32_t T, ChainDp& d, Events& ev, sa_chain_stats& st) {
+void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, uint32_t T, ChainDp& d, ChainTimer& ev, sa_chain_stats& st) {
     const uint32_t N = (uint32_t)n, tiles = (N + T - 1) / T;
     d.N = N;
     Slot* sl = d.sl;
@@ -82,20 +47,13 @@ void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, u
     uint32_t *d_group, *idx_a, *rs, *qs, *ln, *gr, *pred, *first;
     int32_t* sc;
     int64_t* f;
-    auto layout = [&](Take& t) {
-        t(d_hsps, N); t(d_group, N); t(d.key_a, N); t(d.key_b, N); t(idx_a, N); t(d.idx_b, N);
-        t(rs, N); t(qs, N); t(ln, N); t(gr, N); t(sc, N); t(f, N); t(pred, N);
-        t(d.head, (size_t)N + 1); t(d.gidx, (size_t)N + 1); t(first, tiles);
-        t(d.gstart, N); t(d.gend, N); t(d.glen, (size_t)N + 1); t(d.goff, (size_t)N + 1);
-        t(d.d_members, N); t(d.d_nodes, N);
-    };
-    {
-        Take size{nullptr};
-        layout(size);
-        sl->hspchain_work.ensure(size.end, "hsp chain");
-        Take t{sl->hspchain_work.p};
-        layout(t);
-    }
+    carve(sl->hspchain_work, "hsp chain", [&](Carve& c) {
+        c.take(d_hsps, N).take(d_group, N).take(d.key_a, N).take(d.key_b, N).take(idx_a, N).take(d.idx_b, N);
+        c.take(rs, N).take(qs, N).take(ln, N).take(gr, N).take(sc, N).take(f, N).take(pred, N);
+        c.take(d.head, (size_t)N + 1).take(d.gidx, (size_t)N + 1).take(first, tiles);
+        c.take(d.gstart, N).take(d.gend, N).take(d.glen, (size_t)N + 1).take(d.goff, (size_t)N + 1);
+        c.take(d.d_members, N).take(d.d_nodes, N);
+    });
     if (!group) d_group = nullptr;
     sl->hspchain_partial.ensure((size_t)tiles * T * sizeof(HspChainPartial), "hsp chain partials");
     HspChainPartial* partial = (HspChainPartial*)sl->hspchain_partial.p;
@@ -120,16 +78,14 @@ void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, u
     // rank: stable sort by (query_start, len) with the input index as value, then by (group, ref_start); idx_a ends up as rank -> input index
     std::vector<uint32_t> h_first(tiles);
     ev.mark(0);
-    {
-        ProfScope ps(sl, "hspchain_rank");
+    launch(sl, "hspchain_rank", [&] {
         launch_hspchain_key_minor(d_hsps, N, d.key_a, idx_a, s);
         cover_sort_anchors(temp, &d.temp_bytes, d.key_a, d.key_b, idx_a, d.idx_b, N, s);
         launch_hspchain_key_major(d_hsps, d_group, d.idx_b, N, d.key_a, s);
         cover_sort_anchors(temp, &d.temp_bytes, d.key_a, d.key_b, d.idx_b, idx_a, N, s);
         launch_hspchain_gather(d_hsps, d_group, idx_a, N, rs, qs, ln, sc, gr, d.head, s);
         launch_hspchain_first(gr, N, T, first, s);
-        check_launch("hspchain_rank");
-    }
+    });
     ev.mark(1);
     check_memcpy(hipMemcpyAsync(h_first.data(), first, tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "hsp chain: first tiles");
     check_sync(s, "hspchain_rank");
@@ -174,16 +130,6 @@ uint32_t checked(const sa_chain_params* p, size_t n, sa_chain_params& P) {
     return (uint32_t)tile_opt;
 }
 
-void* host_array(size_t count, size_t size) {
-    if (!count) return nullptr;
-    void* p = malloc(count * size);
-    if (!p) {
-        fprintf(stderr, "Error: ChainHsps: out of host memory\n");
-        exit(12);
-    }
-    return p;
-}
-
 }  // namespace
 
 extern "C" {
@@ -201,37 +147,33 @@ size_t sa_chain_hsps(const sa_segment_pair* hsps, size_t n, const uint32_t* grou
     if (n == 0) return 0;
     Slot* sl = d.sl = acquire_slot_early();
     hipStream_t s = sl->stream;
-    Events ev(s, 8);
+    ChainTimer ev(s, "hsp chain timing");
     rank_and_dp(hsps, n, group, T, d, ev, st);
     const uint32_t G = d.G;
 
     // finish: every group's end and chain length, then the members and the nodes
     ev.mark(4);
-    {
-        ProfScope ps(sl, "hspchain_finish");
+    launch(sl, "hspchain_finish", [&] {
         launch_hspchain_group_starts(d.head, d.gidx, d.N, d.gstart, s);
         launch_hspchain_ends(d.a, d.gstart, G, d.P.min_score, d.gend, d.glen, s);
         cover_scan_offsets(d.temp, &d.temp_bytes, d.glen, d.goff, G, s);
-        check_launch("hspchain_finish");
-    }
+    });
     ev.mark(5);
     uint64_t total = 0;
     check_memcpy(hipMemcpyAsync(&total, d.goff + G, sizeof(uint64_t), hipMemcpyDeviceToHost, s), "hsp chain: members");
     check_sync(s, "hspchain_finish");
     ev.mark(6);
-    {
-        ProfScope ps(sl, "hspchain_finish");
+    launch(sl, "hspchain_finish", [&] {
         launch_hspchain_members(d.a, d.order, d.gend, d.glen, d.goff, G, d.d_members, s);
         if (nodes) launch_hspchain_nodes(d.a, d.order, d.d_nodes, s);
-        check_launch("hspchain_finish");
-    }
+    });
     ev.mark(7);
-    sa_chain_member* m_out = (sa_chain_member*)host_array(total, sizeof(sa_chain_member));
-    sa_chain_node* n_out = nodes ? (sa_chain_node*)host_array(n, sizeof(sa_chain_node)) : nullptr;
+    sa_chain_member* m_out = host_alloc<sa_chain_member>(total, "ChainHsps");
+    sa_chain_node* n_out = nodes ? host_alloc<sa_chain_node>(n, "ChainHsps") : nullptr;
     if (total) check_memcpy(hipMemcpyAsync(m_out, d.d_members, total * sizeof(sa_chain_member), hipMemcpyDeviceToHost, s), "hsp chain: members");
     if (nodes) check_memcpy(hipMemcpyAsync(n_out, d.d_nodes, n * sizeof(sa_chain_node), hipMemcpyDeviceToHost, s), "hsp chain: nodes");
     check_sync(s, "hspchain_finish");
-    st.kernel_ms = ev.total(0, 4);
+    st.kernel_ms = ev.ms(0, 1) + ev.ms(2, 3) + ev.ms(4, 5) + ev.ms(6, 7);
     prof_flush(sl);
     release_slot(sl);
 
@@ -268,7 +210,7 @@ size_t sa_chain_hsps_all(const sa_segment_pair* hsps, size_t n, const uint32_t* 
     if (n == 0) return 0;
     Slot* sl = d.sl = acquire_slot_early();
     hipStream_t s = sl->stream;
-    Events ev(s, 10);
+    ChainTimer ev(s, "hsp chain timing");
     rank_and_dp(hsps, n, group, T, d, ev, st.chain);
     const uint32_t N = d.N;
 
@@ -277,24 +219,16 @@ size_t sa_chain_hsps_all(const sa_segment_pair* hsps, size_t n, const uint32_t* 
     a.n = N;
     a.min_score = d.P.min_score;
     a.key_a = d.key_a; a.key_b = d.key_b;  // free since the rank step
-    auto layout = [&](Take& t) {
-        t(a.idx_a, N); t(a.idx_b, N); t(a.byprio, N); t(a.val, N); t(a.ptr_a, N); t(a.ptr_b, N); t(a.head, N); t(a.cscore, N);
-        t(a.cjoin, N); t(a.corder, N); t(a.cpos, N); t(a.keep, (size_t)N + 1); t(a.kidx, (size_t)N + 1); t(a.khead, N);
-        t(a.first, (size_t)N + 1); t(a.tot, 3); t(a.chains, N); t(a.members, N); t(a.chain_of, N);
-    };
-    {
-        Take size{nullptr};
-        layout(size);
-        sl->hsppeel_work.ensure(size.end, "hsp peel");
-        Take t{sl->hsppeel_work.p};
-        layout(t);
-    }
+    carve(sl->hsppeel_work, "hsp peel", [&](Carve& c) {
+        c.take(a.idx_a, N).take(a.idx_b, N).take(a.byprio, N).take(a.val, N).take(a.ptr_a, N).take(a.ptr_b, N).take(a.head, N);
+        c.take(a.cscore, N).take(a.cjoin, N).take(a.corder, N).take(a.cpos, N).take(a.keep, (size_t)N + 1).take(a.kidx, (size_t)N + 1);
+        c.take(a.khead, N).take(a.first, (size_t)N + 1).take(a.tot, 3).take(a.chains, N).take(a.members, N).take(a.chain_of, N);
+    });
     uint32_t rounds = 1;
     while (rounds < 32 && ((uint64_t)1 << rounds) < N) rounds++;  // max(1, ceil(log2 n)): a pred walk has fewer than n links
 
     ev.mark(4);
-    {
-        ProfScope ps(sl, "hsppeel_subtree");
+    launch(sl, "hsppeel_subtree", [&] {
         launch_hsppeel_prio_key(a, s);
         cover_sort_anchors(d.temp, &d.temp_bytes, a.key_a, a.key_b, a.idx_a, a.byprio, N, s);  // stable: equal f stay in rank order
         launch_hsppeel_init(a, s);
@@ -305,12 +239,9 @@ size_t sa_chain_hsps_all(const sa_segment_pair* hsps, size_t n, const uint32_t* 
             ptr = next;
         }
         launch_hsppeel_tails(a, s);
-        check_launch("hsppeel_subtree");
-    }
-    ev.mark(5);
-    ev.mark(6);
-    {
-        ProfScope ps(sl, "hsppeel_order");
+    });
+    ev.mark(5);  // ends the subtree span and starts the order span: nothing is enqueued between the two
+    launch(sl, "hsppeel_order", [&] {
         // the chains by (group, score descending, head rank): the minor sort starts from rank order, both sorts are stable
         launch_hsppeel_chain_key_minor(a, s);
         cover_sort_anchors(d.temp, &d.temp_bytes, a.key_a, a.key_b, a.idx_a, a.idx_b, N, s);
@@ -319,21 +250,17 @@ size_t sa_chain_hsps_all(const sa_segment_pair* hsps, size_t n, const uint32_t* 
         launch_hsppeel_keep(a, s);
         cover_scan_offsets(d.temp, &d.temp_bytes, a.keep, a.kidx, N, s);
         launch_hsppeel_assign(a, s);
-        check_launch("hsppeel_order");
-    }
-    ev.mark(7);
-    ev.mark(8);
-    {
-        ProfScope ps(sl, "hsppeel_members");
+    });
+    ev.mark(6);  // likewise for the order and the members span
+    launch(sl, "hsppeel_members", [&] {
         // the nodes by chain: they start in rank order, so the stable sort leaves a chain's members in rank order
         launch_hsppeel_node_key(a, s);
         cover_sort_anchors(d.temp, &d.temp_bytes, a.key_a, a.key_b, a.idx_a, a.idx_b, N, s);
         launch_hsppeel_members(a, a.key_b, a.idx_b, s);
         launch_hsppeel_records(a, s);
         if (nodes) launch_hspchain_nodes(d.a, d.order, d.d_nodes, s);
-        check_launch("hsppeel_members");
-    }
-    ev.mark(9);
+    });
+    ev.mark(7);
     uint64_t tot[3] = {0, 0, 0};
     check_memcpy(hipMemcpyAsync(tot, a.tot, sizeof(tot), hipMemcpyDeviceToHost, s), "hsp peel: totals");
     check_sync(s, "hsppeel");
@@ -343,17 +270,17 @@ size_t sa_chain_hsps_all(const sa_segment_pair* hsps, size_t n, const uint32_t* 
                 (unsigned long long)tot[2], (unsigned long long)tot[1], n);
         exit(15);
     }
-    sa_chain_record* c_out = (sa_chain_record*)host_array(K, sizeof(sa_chain_record));
-    sa_chain_all_member* m_out = (sa_chain_all_member*)host_array(M, sizeof(sa_chain_all_member));
-    sa_chain_node* n_out = nodes ? (sa_chain_node*)host_array(n, sizeof(sa_chain_node)) : nullptr;
-    uint32_t* o_out = chain_of ? (uint32_t*)host_array(n, sizeof(uint32_t)) : nullptr;
+    sa_chain_record* c_out = host_alloc<sa_chain_record>(K, "ChainHsps");
+    sa_chain_all_member* m_out = host_alloc<sa_chain_all_member>(M, "ChainHsps");
+    sa_chain_node* n_out = nodes ? host_alloc<sa_chain_node>(n, "ChainHsps") : nullptr;
+    uint32_t* o_out = chain_of ? host_alloc<uint32_t>(n, "ChainHsps") : nullptr;
     if (K) check_memcpy(hipMemcpyAsync(c_out, a.chains, K * sizeof(sa_chain_record), hipMemcpyDeviceToHost, s), "hsp peel: chains");
     if (M) check_memcpy(hipMemcpyAsync(m_out, a.members, M * sizeof(sa_chain_all_member), hipMemcpyDeviceToHost, s), "hsp peel: members");
     if (nodes) check_memcpy(hipMemcpyAsync(n_out, d.d_nodes, n * sizeof(sa_chain_node), hipMemcpyDeviceToHost, s), "hsp peel: nodes");
     if (chain_of) check_memcpy(hipMemcpyAsync(o_out, a.chain_of, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "hsp peel: chain_of");
     check_sync(s, "hsppeel");
-    st.chain.kernel_ms = ev.total(0, 2);
-    st.peel_ms = ev.total(2, 3);
+    st.chain.kernel_ms = ev.ms(0, 1) + ev.ms(2, 3);
+    st.peel_ms = ev.ms(4, 5) + ev.ms(5, 6) + ev.ms(6, 7);
     prof_flush(sl);
     release_slot(sl);
 

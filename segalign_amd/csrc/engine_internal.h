@@ -13,6 +13,13 @@
 //   api_rm.hip         repeat-masker entries and the device-side coverage post-processing
 //   api_gapped.hip     sa_gapped_extend / _align / _align_greedy: gapped extension of HSP anchors, paths, cover (gapped.hip, cover.hip)
 //   api_hspchain.hip   sa_chain_hsps: the best collinear chain of every group of HSPs (hspchain.hip); sa_chain_hsps_all: all chains (hsppeel.hip)
+//   api_stitch.hip     sa_stitch_chains: every chain of HSPs as one gapped alignment through its members (stitch.hip, gapped.hip's walk)
+//   post_host.h        what those three share on the host: event timing, checked launches, buffer carving, caller-owned arrays, trace batches
+//   gapped.hip         kernels of the gapped entries: y-drop extension of a side, trace sweep, path walk (gapped.h)
+//   cover.hip          kernels and rocPRIM steps of the greedy cover index; its sort and scan wrappers also serve api_hspchain.hip (gapped.h)
+//   hspchain.hip       kernels of the chaining DP: rank keys, gather, tile cross / resolve, group ends, members, nodes (hspchain.h)
+//   hsppeel.hip        kernels of the peel into all chains: subtree minimum, chain order, members, records (hsppeel.h)
+//   stitch.hip         kernels of the stitch: member scores, the global sweep of a link in five instances (stitch.h)
 //   api_introspect.hip statistics, lookup mode, copies of device state for the tests
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,4 +1,5 @@
-// gapped.h -- what gapped.hip (the kernel) and api_gapped.hip (sa_gapped_extend) share.
+// gapped.h -- what the kernel units gapped.hip and cover.hip share with the host code that launches them: api_gapped.hip (the three gapped
+// entries), api_stitch.hip (the walk and the trace layout), api_hspchain.hip (cover.hip's rocPRIM wrappers) and post_host.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,4 +1,4 @@
-// stitch.h -- what stitch.hip (the kernels) and api_stitch.hip (sa_stitch_chains) share.
+// stitch.h -- what stitch.hip (the kernels) and api_stitch.hip (sa_stitch_chains) share; the link's trace area and its walk are gapped.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
