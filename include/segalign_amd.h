@@ -806,6 +806,82 @@ size_t sa_stitch_chains(const sa_segment_pair* hsps, size_t n_hsps, const uint32
                         sa_stitch_link** links, size_t* n_links, sa_stitch_stats* stats);
 void sa_free_stitch(sa_stitch_record* records, uint32_t* ops, sa_stitch_link* links);
 
+/* ---- netting the chains of a target into fills and gaps (additive; restated by tests/net_model.py) ----------
+ *
+ * sa_net_chains decides which chain to believe where chains overlap on one axis, in the spirit of UCSC's chainNet (not claimed to
+ * equal it): chains are laid on the axis best first, each fills only what is still open, and the gaps inside a fill are open for lower
+ * chains one level down.  It reads no sequence and no table: it needs sa_initialize_interface only.
+ *   Input, one axis at a time: n_chains <= 4 194 304 chains in CSR form, chain c being the blocks first[c] .. first[c + 1] - 1 of
+ *     block_start[] / block_end[] (half-open intervals, at most 1 << 26 in all, every coordinate < 2^31); score[n_chains] (int64);
+ *     group[n_chains] (NULL: one group; ids need be neither sorted nor dense).  Chains of different groups never interact: on the
+ *     target axis a group is a target record.  A chain may be empty; an empty chain never fills.
+ *   Validation (one linear pass; a message and exit code 1, like the other entries): first[0] = 0 and first[] does not decrease; every
+ *     block has start < end < 2^31; the blocks of a chain ascend and are disjoint (end_k <= start_k+1); min_space and min_fill are at most
+ *     1 << 31; the limits above.
+ *   Priority: within a group u comes before v iff score(u) > score(v), or the scores are equal and u's input index is lower.
+ *   Sequential rule: per group the open spaces start as the one root space [0, 2^31) with parent -1 and depth 0.  A space [a, b) is
+ *     searched only if b - a >= min_space.  Chains are taken in priority order; for chain c and every searched space S: clip c's blocks
+ *     to S; if the clipped blocks hold at least max(1, min_fill) bases, c fills S.  The fill is [start of the first clipped block, end of
+ *     the last clipped block) and ali is the clipped base count.  S is replaced by its left remainder [a, fill.start) and its right
+ *     remainder [fill.end, b), which keep S's parent and depth, and the gap between every two consecutive clipped blocks becomes a new
+ *     space with parent = this fill and depth + 1.
+ *   Equivalent rule (what the device computes): the chain that fills a space is the chain of best priority that qualifies in it; then
+ *     the same for its remainders and gaps.  Clipped bases only shrink with the space, so whatever qualifies in a remainder or gap comes
+ *     after the space's filler, and a new space is scanned from the position after its opener's.
+ *   Consequence: at min_space = min_fill = 1 the clipped blocks of all fills partition the union of all blocks of the group, and every
+ *     base belongs to the chain of best priority with a block over it.
+ *   Output: one sa_net_fill per fill, ordered by (group ascending, start ascending).  Starts are unique within a group (a child starts
+ *     strictly inside its parent, fills of sibling spaces are disjoint), so this order is the pre-order walk of the net.  parent is an
+ *     index into the output, or -1; first_block is the absolute index, in the block arrays, of the first clipped block; the clipped
+ *     blocks of a fill are the blocks first_block .. first_block + n_blocks - 1 intersected with [start, end); score is the chain's.
+ * The device runs level-synchronous rounds over the open spaces, one wavefront per space; the worst case is one round per fill along a
+ * line.  More than 2^31 - 1 fills end the process with a message.  Slots and thread safety are those of sa_chain_hsps. */
+typedef struct sa_net_params {
+    uint32_t min_space; /* spaces shorter than this are not searched; 0 = 1; at most 1 << 31 */
+    uint32_t min_fill;  /* a chain fills a space only with at least this many clipped bases; 0 = 1; at most 1 << 31 */
+} sa_net_params;
+
+typedef struct sa_net_fill { /* 48 bytes */
+    uint32_t group;
+    uint32_t chain;       /* input index of the chain */
+    int32_t parent;       /* index of the fill whose gap this one lies in, or -1 */
+    uint32_t depth;       /* 0 for a fill of the root space */
+    uint32_t start, end;
+    uint32_t ali;         /* clipped bases */
+    uint32_t first_block; /* absolute index of the first clipped block */
+    uint32_t n_blocks;
+    uint32_t pad;
+    int64_t score;        /* the chain's score */
+} sa_net_fill;
+
+typedef struct sa_net_stats {
+    uint64_t chains;
+    uint64_t blocks;
+    uint64_t groups;    /* groups that hold a chain */
+    uint64_t fills;
+    uint64_t spaces;    /* spaces searched, summed over the rounds */
+    uint64_t rounds;
+    uint64_t max_depth;
+    uint64_t filled;    /* chains with at least one fill */
+    float prep_ms;      /* device time of the priority order, hulls and prefix sums */
+    float net_ms;       /* device time of the rounds and the final order */
+} sa_net_stats;
+#ifdef __cplusplus
+static_assert(sizeof(sa_net_params) == 8, "sa_net_params is 8 bytes");
+static_assert(sizeof(sa_net_fill) == 48, "sa_net_fill is 48 bytes");
+static_assert(sizeof(sa_net_stats) == 72, "sa_net_stats is 72 bytes");
+#else
+_Static_assert(sizeof(sa_net_params) == 8, "sa_net_params is 8 bytes");
+_Static_assert(sizeof(sa_net_fill) == 48, "sa_net_fill is 48 bytes");
+_Static_assert(sizeof(sa_net_stats) == 72, "sa_net_stats is 72 bytes");
+#endif
+
+/* Returns the number of fills.  *fills is malloc-ed and released with sa_free_net; it is NULL when there are none.  group: nullable.
+ * p: NULL takes the defaults.  stats: nullable. */
+size_t sa_net_chains(const uint32_t* first, const uint32_t* block_start, const uint32_t* block_end, const int64_t* score,
+                     const uint32_t* group, size_t n_chains, const sa_net_params* p, sa_net_fill** fills, sa_net_stats* stats);
+void sa_free_net(sa_net_fill* fills);
+
 const char* sa_version(void);
 
 #ifdef __cplusplus

@@ -132,6 +132,10 @@ void slot_destroy(Slot& s) {
     s.hspchain_temp.release("hsp chain temp");
     s.hsppeel_work.release("hsp peel");
     s.stitch.release("stitch");
+    s.net_work.release("net");
+    s.net_round.release("net round");
+    s.net_fills.release("net fills");
+    for (int i = 0; i < 2; i++) s.net_space[i].release("net spaces");
     s.cand_list.release("candidate list");
     s.l2_list.release("second-level list");
     s.audit.release("audit list");

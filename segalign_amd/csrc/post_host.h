@@ -1,4 +1,4 @@
-// post_host.h -- the host helpers that the post-processing entries share (api_gapped.hip, api_hspchain.hip, api_stitch.hip):
+// post_host.h -- the host helpers that the post-processing entries share (api_gapped.hip, api_hspchain.hip, api_stitch.hip, api_net.hip):
 // device time between events, profiled and checked launches, carving a slot buffer, malloc-ed arrays for the caller, the resident block
 // as kernel arguments, and the trace batches' packing and runs.  Host code only, everything inline or a template.
 #pragma once

@@ -42,6 +42,7 @@ C_ABI_SYMBOLS = [
     "sa_gapped_extend", "sa_free_gapped", "sa_gapped_align", "sa_free_gapped_align", "sa_gapped_align_greedy",
     "sa_chain_hsps", "sa_free_chain", "sa_chain_hsps_all", "sa_free_chain_all",
     "sa_stitch_chains", "sa_free_stitch",
+    "sa_net_chains", "sa_free_net",
 ]
 IVL_DTYPE = np.dtype([("query_start", "<u4"), ("len", "<u4")])  # struct Segment, repeat_masker_src/graph.h:32-35
 STRAND_PLUS, STRAND_MINUS, STRAND_BOTH = 1, 2, 3
@@ -117,6 +118,19 @@ class StitchStats(C.Structure):
     _fields_ = [("links", C.c_uint64), ("swept", C.c_uint64), ("long_links", C.c_uint64), ("dead_links", C.c_uint64),
                 ("low_links", C.c_uint64), ("cells", C.c_uint64), ("records", C.c_uint64), ("member_ms", C.c_double),
                 ("sweep_ms", C.c_double), ("walk_ms", C.c_double), ("trace_bytes", C.c_uint64), ("batches", C.c_uint64)]
+
+
+NET_FILL_DTYPE = np.dtype([("group", "<u4"), ("chain", "<u4"), ("parent", "<i4"), ("depth", "<u4"), ("start", "<u4"), ("end", "<u4"),
+                           ("ali", "<u4"), ("first_block", "<u4"), ("n_blocks", "<u4"), ("pad", "<u4"), ("score", "<i8")])  # sa_net_fill
+
+
+class NetParams(C.Structure):
+    _fields_ = [("min_space", C.c_uint32), ("min_fill", C.c_uint32)]
+
+
+class NetStats(C.Structure):
+    _fields_ = [("chains", C.c_uint64), ("blocks", C.c_uint64), ("groups", C.c_uint64), ("fills", C.c_uint64), ("spaces", C.c_uint64),
+                ("rounds", C.c_uint64), ("max_depth", C.c_uint64), ("filled", C.c_uint64), ("prep_ms", C.c_float), ("net_ms", C.c_float)]
 
 
 class CallStats(C.Structure):
@@ -238,6 +252,10 @@ def lib():
                                    C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
                                    C.POINTER(C.c_size_t), C.POINTER(StitchStats)]
     L.sa_free_stitch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sa_net_chains.restype = C.c_size_t
+    L.sa_net_chains.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(NetParams),
+                                C.POINTER(C.c_void_p), C.POINTER(NetStats)]
+    L.sa_free_net.argtypes = [C.c_void_p]
     _lib = L
     return L
 
@@ -566,6 +584,40 @@ def StitchChains(hsps, members, first, rev, buffer=0, gap_open=400, gap_extend=3
     res_l = _chain_take(lnk, n_links.value, STITCH_LINK_DTYPE)
     lib().sa_free_stitch(rec, ops, lnk)
     return (res_r, res_o, res_l, _flat(st)) if links else (res_r, res_o, _flat(st))
+
+
+def net_blocks(hsps, members, first, axis="target"):
+    """The chains of chain_csr as NetChains takes them on one axis: every member HSP gives the block [start, start + len + 1) there.
+    Rank order makes the blocks of a chain ascending and disjoint on both axes.  -> (block_start, block_end), uint32, first unchanged."""
+    if axis not in ("target", "query"):
+        raise ValueError("axis: target or query")
+    h = np.ascontiguousarray(hsps, dtype=SEG_DTYPE)[np.asarray(members, dtype=np.int64)]
+    if int(np.asarray(first)[-1]) != h.size:
+        raise ValueError("first: one offset per chain and the number of members at the end")
+    start = h["ref_start" if axis == "target" else "query_start"].astype(np.uint32)
+    return start, (start + h["len"] + np.uint32(1)).astype(np.uint32)
+
+
+def NetChains(first, block_start, block_end, score, group=None, min_space=1, min_fill=1):
+    """The chains of every group netted into fills and gaps on one axis (sa_net_chains; contract in include/segalign_amd.h).
+    Chain c is the half-open blocks first[c] .. first[c + 1] - 1 of block_start / block_end (see net_blocks); score: one int64 per chain;
+    group: one uint32 per chain (None: one group).  -> (NET_FILL_DTYPE fills ordered by (group, start), stats dict).  Needs
+    InitializeInterface only."""
+    f = np.ascontiguousarray(first, dtype=np.uint32)
+    bs = np.ascontiguousarray(block_start, dtype=np.uint32)
+    be = np.ascontiguousarray(block_end, dtype=np.uint32)
+    sc = np.ascontiguousarray(score, dtype=np.int64)
+    g = None if group is None else np.ascontiguousarray(group, dtype=np.uint32)
+    n = f.size - 1
+    if n < 0 or sc.size != n or (g is not None and g.size != n) or bs.size != be.size or bs.size < int(f.max()):
+        raise ValueError("first: one offset per chain and one more; score, group: one entry per chain; blocks: first[-1] of each")
+    p, out, st = NetParams(int(min_space), int(min_fill)), C.c_void_p(), NetStats()
+    k = lib().sa_net_chains(f.ctypes.data, bs.ctypes.data if bs.size else None, be.ctypes.data if be.size else None,
+                            sc.ctypes.data if n else None, g.ctypes.data if g is not None and n else None, n, C.byref(p), C.byref(out),
+                            C.byref(st))
+    res = _chain_take(out, k, NET_FILL_DTYPE)
+    lib().sa_free_net(out)
+    return res, _flat(st)
 
 
 def cigar(ops):

@@ -53,6 +53,10 @@ struct Config {  // src/graph.h:32-76 with the defaults of src/main.cpp:61-124
     uint32_t stitch_max_link = 0;  // sa_stitch_params.max_link; 0: the engine's default
     bool stitch_min_set = false;
     int stitch_min = INT32_MIN;    // --gpu_stitch_min=N: sa_stitch_params.min_link_score
+    bool gpu_net = false;     // --gpu_net[=min_space] (with --gpu_chain_all): a .net file next to every .chains file (sa_net_chains on the target axis)
+    uint32_t net_space = 0;   // sa_net_params.min_space; 0: the engine's default
+    bool net_fill_set = false;
+    uint32_t net_fill = 0;    // --gpu_net_fill=N: sa_net_params.min_fill
     int gap_open = 400, gap_extend = 30;
     int xdrop = 910, hspthresh = 3000, ydrop = 9430, gappedthresh = -1;
     uint32_t wga_chunk = 250000, lastz_interval = 10000000, seq_block_size = 500000000;
@@ -266,7 +270,9 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
             std::string cname = base + (cfg.gpu_chain ? ".chain" : ".chains");
             f = fopen((cfg.outdir + "/" + cname).c_str(), "w");
             if (!f) die(7, "cant open file: %s", cname.c_str());
-            std::vector<uint32_t> idx, cfirst(1, 0);  // cfirst: the chains' offsets into the members, for --gpu_stitch
+            std::vector<uint32_t> idx, cfirst(1, 0);  // cfirst: the chains' offsets into the members, for --gpu_stitch and --gpu_net
+            std::vector<int64_t> cscore;              // with --gpu_net: every kept chain's score and the target record of its pair
+            std::vector<uint32_t> ctarget;
             if (cfg.gpu_chain) {
                 sa_chain_member* mem = nullptr;
                 const size_t nm = sa_chain_hsps(v.data(), v.size(), group.data(), &cp, &mem, nullptr, nullptr);
@@ -286,6 +292,10 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
                             ch[c].joined >= 0 ? 1 : 0);
                     for (size_t k = ch[c].first_member; k < (size_t)ch[c].first_member + ch[c].n_members; k++) { emit(v[mem[k].hsp_index]); idx[k] = mem[k].hsp_index; }
                     cfirst.push_back(ch[c].first_member + ch[c].n_members);  // the chains' members follow one another
+                    if (cfg.gpu_net) {
+                        cscore.push_back(ch[c].score);
+                        ctarget.push_back((uint32_t)(pairs[ch[c].group] >> 32));
+                    }
                 }
                 sa_free_chain_all(ch, mem, nullptr, nullptr);
             }
@@ -322,6 +332,33 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
                 }
                 fclose(sf);
                 sa_free_stitch(sr, sops, nullptr);
+            }
+            if (cfg.gpu_net) {  // which chain to believe where: the kept chains of every target record netted on the target axis
+                std::vector<uint32_t> bs(idx.size()), be(idx.size());  // a member is one block, in block coordinates
+                for (size_t k = 0; k < idx.size(); k++) {
+                    bs[k] = v[idx[k]].ref_start;
+                    be[k] = v[idx[k]].ref_start + v[idx[k]].len + 1;
+                }
+                sa_net_params np = {cfg.net_space, cfg.net_fill};
+                sa_net_fill* nf = nullptr;
+                const size_t nn = sa_net_chains(cfirst.data(), bs.data(), be.data(), cscore.data(), ctarget.data(), cfirst.size() - 1, &np, &nf, nullptr);
+                std::string nname = base + ".net";
+                FILE* nfp = fopen((cfg.outdir + "/" + nname).c_str(), "w");
+                if (!nfp) die(7, "cant open file: %s", nname.c_str());
+                for (size_t k = 0; k < nn; k++) {  // the order sa_net_chains returns: by target record, then the pre-order walk of its net
+                    const sa_net_fill& x = nf[k];
+                    const size_t ri = x.group;
+                    if (k == 0 || nf[k - 1].group != x.group) fprintf(nfp, "net %s %u\n", R.chr_name[ri].c_str(), R.chr_len[ri]);
+                    // an HSP is ungapped: a clip on the target shifts the query by the same amount
+                    const uint32_t k0 = x.first_block, k1 = x.first_block + x.n_blocks - 1;
+                    const size_t q0 = (size_t)v[idx[k0]].query_start + (x.start - bs[k0]) + q_block_start;
+                    const size_t q1 = (size_t)v[idx[k1]].query_start + (x.end - bs[k1]) + q_block_start;
+                    const size_t qi = chr_of(qs, q0);
+                    fprintf(nfp, "%*sfill %zu %u %s %c %zu %zu chain=%u score=%lld ali=%u\n", (int)x.depth, "", x.start + r_block_start - R.chr_start[ri],
+                            x.end - x.start, qn[qi].c_str(), rev ? '-' : '+', q0 - qs[qi], q1 - q0, x.chain, (long long)x.score, x.ali);
+                }
+                fclose(nfp);
+                sa_free_net(nf);
             }
             std::sort(idx.begin(), idx.end());  // an HSP is a member of one chain at most: no duplicates
             kept.reserve(idx.size());
@@ -424,7 +461,12 @@ static void usage() {
             "  --gpu_stitch[=max_link] (with --gpu_chain or --gpu_chain_all: a .stitched.maf file next to each .chain / .chains file with every\n"
             "      chain as one alignment through all its members, the stretch between two members aligned globally with --gap=O,E; a chain\n"
             "      is cut where a side of that stretch exceeds max_link (default and at most 2048) or holds a record boundary)\n"
-            "  --gpu_stitch_min=N (with --gpu_stitch: a chain is also cut at a stretch whose alignment scores less than N)\n");
+            "  --gpu_stitch_min=N (with --gpu_stitch: a chain is also cut at a stretch whose alignment scores less than N)\n"
+            "  --gpu_net[=min_space] (with --gpu_chain_all: a .net file next to each .chains file: the kept chains of every target record laid\n"
+            "      on the target best first, each filling what is still open, the gaps inside a fill open to lower chains one level down; a\n"
+            "      line 'net <target record> <length>' per record, then per fill, indented by its depth, 'fill <tstart> <tsize> <qname> <+|->\n"
+            "      <qstart> <qsize> chain=<k> score=<s> ali=<n>'; open stretches shorter than min_space, default 1, are not searched)\n"
+            "  --gpu_net_fill=N (with --gpu_net: a chain fills an open stretch only with at least N bases in it; default 1)\n");
 }
 
 int main(int argc, char** argv) {
@@ -506,6 +548,21 @@ int main(int argc, char** argv) {
             cfg.stitch_min = (int)ms;
             cfg.stitch_min_set = true;
         }
+        else if (!strcmp(a, "--gpu_net")) cfg.gpu_net = true;
+        else if (opt(a, "--gpu_net", v)) {
+            char* endp = nullptr;
+            const long long ms = strtoll(v.c_str(), &endp, 10);
+            if (endp == v.c_str() || *endp || ms < 1 || ms > (1ll << 31)) { fprintf(stderr, "bad --gpu_net=%s (min_space: 1 .. 2147483648)\n", v.c_str()); return 1; }
+            cfg.gpu_net = true;
+            cfg.net_space = (uint32_t)ms;
+        }
+        else if (opt(a, "--gpu_net_fill", v)) {
+            char* endp = nullptr;
+            const long long mf = strtoll(v.c_str(), &endp, 10);
+            if (endp == v.c_str() || *endp || mf < 1 || mf > (1ll << 31)) { fprintf(stderr, "bad --gpu_net_fill=%s (1 .. 2147483648)\n", v.c_str()); return 1; }
+            cfg.net_fill = (uint32_t)mf;
+            cfg.net_fill_set = true;
+        }
         else if (opt(a, "--gap", v)) {
             if (sscanf(v.c_str(), "%d,%d", &cfg.gap_open, &cfg.gap_extend) != 2) { fprintf(stderr, "bad --gap=%s\n", v.c_str()); return 1; }
         }
@@ -520,6 +577,8 @@ int main(int argc, char** argv) {
     if (cfg.chain_min_set && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_chain_min needs --gpu_chain_all\n"); return 1; }
     if (cfg.gpu_stitch && !cfg.gpu_chain && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_stitch needs --gpu_chain or --gpu_chain_all\n"); return 1; }
     if (cfg.stitch_min_set && !cfg.gpu_stitch) { fprintf(stderr, "--gpu_stitch_min needs --gpu_stitch\n"); return 1; }
+    if (cfg.gpu_net && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_net needs --gpu_chain_all\n"); return 1; }
+    if (cfg.net_fill_set && !cfg.gpu_net) { fprintf(stderr, "--gpu_net_fill needs --gpu_net and --gpu_chain_all\n"); return 1; }
     cfg.target = pos[0];
     cfg.query = pos[1];
     if (pos.size() > 2) cfg.data_folder = pos[2];

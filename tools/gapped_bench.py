@@ -24,8 +24,13 @@ adds the links by sweep instance, the broken links by reason, the cells, member 
 trace bytes and batches, and the target bases the stitched records span beside those the gapped alignments of the same members span.
 Records, ops and links are checked against the model (tests/stitch_model.py) once per run.
 
+With --net [--net-space N] [--net-fill N] (which implies --chain-all) the kept chains go through sa_net_chains on the target axis
+(DESIGN.md 19): the line then adds the chains and blocks, fills, rounds, spaces searched, max depth, chains without a fill, prep ms and
+net ms beside peel ms and the DP's kernel ms.  The fills are checked against the model (tests/net_model.py) once per run.
+
   python tools/gapped_bench.py [--workloads standin,lumpy] [--repeat 3] [--align] [--greedy] [--batches 1024,2048,...]
                                [--pieces N] [--max-extent M] [--chain] [--chain-pen D,A] [--chain-all] [--chain-min N] [--stitch] [--stitch-max-link N]
+                               [--net] [--net-space N] [--net-fill N]
 """
 import argparse
 import functools
@@ -195,7 +200,32 @@ def stitch_fields(hsps, members, repeat, max_link):
             "kept_gapped_alignments": int(grecs.size), "stitch_model_checked": True, "stitch_model_s": round(model_s, 1)}
 
 
-def chain_all_fields(hsps, repeat, pen, min_score, dp, align, greedy, stitch=None):
+def net_fields(hsps, chains, members, repeat, net, peel_ms, dp_ms):
+    """sa_net_chains on the kept chains' target blocks, the run with the least net time, checked against the model."""
+    import net_model as N
+    mem, first = E.chain_csr(members)
+    bs, be = E.net_blocks(hsps, mem, first, axis="target")
+    best = None
+    for _ in range(repeat):
+        t0 = time.perf_counter()
+        r = E.NetChains(first, bs, be, chains["score"], chains["group"], min_space=net[0], min_fill=net[1])
+        wall = (time.perf_counter() - t0) * 1e3
+        if best is None or r[1]["net_ms"] < best[0][1]["net_ms"]:
+            best = (r, wall)
+    (fills, st), wall = best
+    t0 = time.perf_counter()
+    want, want_st = N.net(first, bs, be, chains["score"], chains["group"], min_space=net[0], min_fill=net[1])
+    model_s = time.perf_counter() - t0
+    if not np.array_equal(fills, want.astype(fills.dtype)) or any(st[k] != want_st[k] for k in ("fills", "filled", "max_depth")):
+        raise SystemExit("sa_net_chains differs from the model")
+    return {"net_min_space": int(net[0]), "net_min_fill": int(net[1]), "net_chains": int(st["chains"]), "net_blocks": int(st["blocks"]),
+            "net_fills": int(st["fills"]), "net_rounds": int(st["rounds"]), "net_spaces": int(st["spaces"]), "net_max_depth": int(st["max_depth"]),
+            "net_chains_without_fill": int(st["chains"] - st["filled"]), "net_prep_ms": round(st["prep_ms"], 3), "net_ms": round(st["net_ms"], 3),
+            "net_call_ms": round(wall, 3), "net_over_peel": round(st["net_ms"] / peel_ms, 4) if peel_ms > 0 else None,
+            "net_over_dp": round(st["net_ms"] / dp_ms, 4) if dp_ms > 0 else None, "net_model_checked": True, "net_model_s": round(model_s, 1)}
+
+
+def chain_all_fields(hsps, repeat, pen, min_score, dp, align, greedy, stitch=None, net=None):
     """sa_chain_hsps_all on the HSPs as one group, checked against the numpy model on the DP values `dp` that chain_fields checked, and
     the gapped entries on the kept chains' members."""
     import hsp_chain_all_model as A
@@ -219,10 +249,12 @@ def chain_all_fields(hsps, repeat, pen, min_score, dp, align, greedy, stitch=Non
     out.update(kept_fields(hsps[np.sort(members["hsp_index"])], repeat, align, greedy, "all_kept_"))
     if stitch is not None:
         out.update(stitch_fields(hsps, members, repeat, stitch))
+    if net is not None:
+        out.update(net_fields(hsps, chains, members, repeat, net, st["peel_ms"], st["kernel_ms"]))
     return out
 
 
-def chain_fields(hsps, repeat, pen, align, greedy, all_min=None, stitch=None):
+def chain_fields(hsps, repeat, pen, align, greedy, all_min=None, stitch=None, net=None):
     """sa_chain_hsps on the HSPs as one group, checked against the numpy model, and the gapped entries on the chain's members; with
     all_min also chain_all_fields."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -248,11 +280,11 @@ def chain_fields(hsps, repeat, pen, align, greedy, all_min=None, stitch=None):
            "chain_model_checked": True, "chain_model_s": round(model_s, 1)}
     out.update(kept_fields(kept, repeat, align, greedy, "kept_"))
     if all_min is not None:
-        out.update(chain_all_fields(hsps, repeat, pen, all_min, (f, pred), align, greedy, stitch))
+        out.update(chain_all_fields(hsps, repeat, pen, all_min, (f, pred), align, greedy, stitch, net))
     return out
 
 
-def run(name, repeat, align=False, greedy=False, with_sel=True, pieces=0, chain=None, chain_all_min=None, stitch=None):
+def run(name, repeat, align=False, greedy=False, with_sel=True, pieces=0, chain=None, chain_all_min=None, stitch=None, net=None):
     t, q = workload(name)
     if greedy or pieces:
         E.set_option("debug", 1)  # sa_gapped_align_greedy then prints its edge count, the continuation its pieces
@@ -300,7 +332,7 @@ def run(name, repeat, align=False, greedy=False, with_sel=True, pieces=0, chain=
     if greedy:
         extra.update(greedy_fields(hsps, repeat, with_sel))
     if chain is not None:
-        extra.update(chain_fields(hsps, repeat, chain, align, greedy, chain_all_min, stitch))
+        extra.update(chain_fields(hsps, repeat, chain, align, greedy, chain_all_min, stitch, net))
     E.ShutdownProcessor()
     if greedy or pieces:
         E.reset_option("debug")
@@ -328,15 +360,18 @@ def main():
     ap.add_argument("--chain-min", type=int, default=0, help="with --chain-all: min_score")
     ap.add_argument("--stitch", action="store_true", help="also stitch the kept chains (sa_stitch_chains); implies --chain-all")
     ap.add_argument("--stitch-max-link", type=int, default=0, help="with --stitch: max_link (0: the default, 2048)")
+    ap.add_argument("--net", action="store_true", help="also net the kept chains on the target axis (sa_net_chains); implies --chain-all")
+    ap.add_argument("--net-space", type=int, default=1, help="with --net: min_space")
+    ap.add_argument("--net-fill", type=int, default=1, help="with --net: min_fill")
     a = ap.parse_args()
-    a.chain_all = a.chain_all or a.stitch
+    a.chain_all = a.chain_all or a.stitch or a.net
     chain = tuple(int(x) for x in a.chain_pen.split(",")) if a.chain or a.chain_all else None
     if a.max_extent:
         KW["max_extent"] = a.max_extent
     for name in a.workloads.split(","):
         if not a.batches:
             print(json.dumps(run(name, a.repeat, a.align, a.greedy, pieces=a.pieces, chain=chain, chain_all_min=a.chain_min if a.chain_all else None,
-                                 stitch=a.stitch_max_link if a.stitch else None)), flush=True)
+                                 stitch=a.stitch_max_link if a.stitch else None, net=(a.net_space, a.net_fill) if a.net else None)), flush=True)
             continue
         for b in a.batches.split(","):
             E.set_option("gapped_greedy_batch", int(b))
