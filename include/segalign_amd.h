@@ -701,6 +701,48 @@ size_t sa_chain_hsps_all(const sa_segment_pair* hsps, size_t n, const uint32_t* 
                          sa_chain_all_stats* stats);
 void sa_free_chain_all(sa_chain_record* chains, sa_chain_all_member* members, sa_chain_node* nodes, uint32_t* chain_of);
 
+/* ---- chaining under piecewise-linear gap costs (additive; restated by tests/hsp_chain_gap_model.py) ----------
+ *
+ * sa_chain_hsps_costs and sa_chain_hsps_all_costs are sa_chain_hsps and sa_chain_hsps_all with one more term in the penalty of a
+ * link: a concave, piecewise-linear gap cost in the spirit of axtChain's -linearGap (this project's own; not claimed to equal
+ * axtChain).  A table has separate costs for a gap in the query only, in the target only, and in both.
+ *   Piecewise-linear cost, for one cost array c and a length x >= 1: with k the largest index with pos[k] <= x,
+ *       g(c, x) = c[k] + (((x - pos[k]) * slope_k) >> 16),      and g(c, x) = c[0] if x < pos[0];
+ *     slope_k = floor(65536 * (c[k+1] - c[k]) / (pos[k+1] - pos[k])) for k < n - 1, and slope_{n-1} = slope_{n-2}: the last segment is
+ *     extrapolated.  With n = 1 the slope is 0.  The host derives the slopes once per call; the device never divides.
+ *   Gap cost of a link, with dt = rs_i - re_j and dq = qs_i - qe_j:
+ *       dt = dq = 0: 0;    dt = 0: g(q_gap, dq);    dq = 0: g(t_gap, dt);    otherwise: g(both_gap, dt + dq).
+ *   Penalty: pen'(j, i) = pen(j, i) + gapcost(dt, dq), pen being sa_chain_hsps's linear term; both may be in force at once.
+ *     Predecessor relation, max_gap, recurrence, rank, ties, min_score, output, peel and stats are those of sa_chain_hsps and
+ *     sa_chain_hsps_all, word for word.
+ *   Validation (a message and exit code 1, like the other entries): n in 1 .. 16; pos strictly ascending with pos[0] >= 1; every cost
+ *     of the first n in 0 .. 2^40; each cost array non-decreasing; every slope < 2^27.  Entries past n are not read.
+ *   Bound: x - pos < 2^33 and slope < 2^27, so (x - pos) * slope < 2^33 * 2^27 = 2^60 and a gap cost is < 2^40 + 2^44 < 2^45.  The
+ *     linear terms stay < 2^54 and |f| <= 2^53, so every intermediate stays inside +-2^56, as before.
+ * g == NULL is exactly sa_chain_hsps / sa_chain_hsps_all: same kernels, same results.  sa_chain_gap_preset fills *out with the table
+ * "loose" or "medium" that axtChain's usage text prints (11 break points, q_gap = t_gap) and returns 0, or -1 for another name. */
+#define SA_CHAIN_GAP_POINTS 16
+typedef struct sa_chain_gap_costs {
+    uint32_t n;                            /* break points, 1 .. 16 */
+    uint32_t pad;
+    uint32_t pos[SA_CHAIN_GAP_POINTS];     /* gap lengths, strictly ascending, pos[0] >= 1 */
+    int64_t q_gap[SA_CHAIN_GAP_POINTS];    /* cost at pos[k] of a gap in the query only (dt == 0) */
+    int64_t t_gap[SA_CHAIN_GAP_POINTS];    /* ... in the target only (dq == 0) */
+    int64_t both_gap[SA_CHAIN_GAP_POINTS]; /* ... in both, looked up at dt + dq */
+} sa_chain_gap_costs;
+#ifdef __cplusplus
+static_assert(sizeof(sa_chain_gap_costs) == 456, "sa_chain_gap_costs is 456 bytes");
+#else
+_Static_assert(sizeof(sa_chain_gap_costs) == 456, "sa_chain_gap_costs is 456 bytes");
+#endif
+
+size_t sa_chain_hsps_costs(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p,
+                           const sa_chain_gap_costs* g, sa_chain_member** members, sa_chain_node** nodes, sa_chain_stats* stats);
+size_t sa_chain_hsps_all_costs(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p,
+                               const sa_chain_gap_costs* g, sa_chain_record** chains, size_t* n_chains, sa_chain_all_member** members,
+                               sa_chain_node** nodes, uint32_t** chain_of, sa_chain_all_stats* stats);
+int sa_chain_gap_preset(const char* name, sa_chain_gap_costs* out);
+
 /* ---- stitching the members of a chain into one gapped alignment (additive; restated by tests/cpp/stitch_check.c and
  *      tests/stitch_model.py) ----------------------------------------------------------------------------------------------
  *

@@ -1,10 +1,12 @@
 // api_hspchain.hip -- C-ABI sa_chain_hsps: the best collinear chain of every group of HSPs (contract: include/segalign_amd.h),
-// and sa_chain_hsps_all: all chains of every group, peeled best first.
+// and sa_chain_hsps_all: all chains of every group, peeled best first; sa_chain_hsps_costs and sa_chain_hsps_all_costs:
+// the two under a piecewise-linear gap-cost table, which only picks another pair of DP kernels (hspcost.hip).
 // The host side: checks, the slot, rank (two stable radix sorts) and the tile loop (hspchain.hip: cross, resolve), shared by both; then
 // sa_chain_hsps's finish (group starts, ends, members, nodes) or the peel (hsppeel.hip: subtree minimum, chain order, members), and the
 // counts the kernels' work is reported by.
 #include "post_host.h"  // and through it gapped.h: cover.hip's rocPRIM wrappers cover_sort_anchors, cover_scan_offsets
 #include "hspchain.h"
+#include "hspcost.h"
 #include "hsppeel.h"
 
 using namespace sa;
@@ -35,9 +37,55 @@ struct ChainDp {
     size_t temp_bytes = 0;
 };
 
+// A gap-cost table as the kernels of hspcost.hip read it (layout: hspcost.h), or none: the linear kernels of hspchain.hip.
+struct CostImage {
+    bool on = false;
+    uint32_t w[HSPCOST_WORDS];
+};
+
+void bad_costs(const char* what, unsigned k, long long v) {
+    fprintf(stderr, "Error: ChainHsps: gap costs: %s[%u] = %lld out of range\n", what, k, v);
+    exit(1);
+}
+
+// Checks a table (contract: include/segalign_amd.h), derives the slopes and folds the three cost arrays into the image.
+void checked_costs(const sa_chain_gap_costs* g, CostImage& im) {
+    im.on = g != nullptr;
+    if (!g) return;
+    const uint32_t n = g->n;
+    if (n < 1 || n > SA_CHAIN_GAP_POINTS) bad("gap costs: n", n);
+    for (uint32_t k = 0; k < n; k++)
+        if (k == 0 ? g->pos[0] < 1 : g->pos[k] <= g->pos[k - 1]) bad_costs("pos", k, g->pos[k]);
+    const int64_t* cost[3] = {g->q_gap, g->t_gap, g->both_gap};
+    const char* name[3] = {"q_gap", "t_gap", "both_gap"};
+    const char* slope_name[3] = {"slope of q_gap", "slope of t_gap", "slope of both_gap"};
+    for (uint32_t k = 0; k < HSPCOST_POINTS; k++) im.w[k] = g->pos[std::min(k, n - 1)];
+    for (int a = 0; a < 3; a++) {
+        const int64_t* c = cost[a];
+        uint32_t slope[SA_CHAIN_GAP_POINTS];
+        for (uint32_t k = 0; k < n; k++)
+            if (c[k] < 0 || c[k] > ((int64_t)1 << 40) || (k > 0 && c[k] < c[k - 1])) bad_costs(name[a], k, c[k]);
+        for (uint32_t k = 0; k + 1 < n; k++) {
+            const int64_t sl = ((c[k + 1] - c[k]) << 16) / (int64_t)(g->pos[k + 1] - g->pos[k]);  // operands >= 0: the quotient is the floor
+            if (sl >= (int64_t)HSPCOST_SLOPE_LIMIT) bad_costs(slope_name[a], k, sl);
+            slope[k] = (uint32_t)sl;
+        }
+        slope[n - 1] = n > 1 ? slope[n - 2] : 0;
+        for (uint32_t k = 0; k < HSPCOST_POINTS; k++) {
+            const uint32_t r = std::min(k, n - 1);
+            uint32_t* row = im.w + HSPCOST_ROW0 + 4 * ((uint32_t)a * HSPCOST_POINTS + k);
+            row[0] = (uint32_t)c[r];
+            row[1] = (uint32_t)((uint64_t)c[r] >> 32);
+            row[2] = slope[r];
+            row[3] = g->pos[r];
+        }
+    }
+}
+
 // The slot's buffers, the upload, rank and the DP (spans 0 and 1 of ev) for n > 0 HSPs on the slot d.sl.  Returns with the stream
 // synchronised, G known and st's pair_evals and tile_steps counted.
-void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, uint32_t T, ChainDp& d, ChainTimer& ev, sa_chain_stats& st) {
+void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, uint32_t T, const CostImage& costs, ChainDp& d, ChainTimer& ev,
+                 sa_chain_stats& st) {
     const uint32_t N = (uint32_t)n, tiles = (N + T - 1) / T;
     d.N = N;
     Slot* sl = d.sl;
@@ -63,6 +111,7 @@ void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, u
     d.temp_bytes = std::max(sort_bytes, scan_bytes);
     sl->hspchain_temp.ensure(std::max<size_t>(d.temp_bytes, 256), "hsp chain temp");
     void* temp = d.temp = sl->hspchain_temp.p;
+    if (costs.on) sl->hspcost_image.ensure(sizeof(costs.w), "hsp chain gap costs");
 
     HspChainArgs& a = d.a;
     a.rs = rs; a.qs = qs; a.ln = ln; a.gr = gr; a.sc = sc; a.f = f; a.pred = pred;
@@ -71,9 +120,13 @@ void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, u
     a.diag_pen = d.P.diag_pen;
     a.anti_pen = d.P.anti_pen;
     a.max_gap = d.P.max_gap;
+    HspCostArgs ca;
+    ca.c = a;
+    ca.image = costs.on ? (const uint32_t*)sl->hspcost_image.p : nullptr;
 
     check_memcpy(hipMemcpyAsync(d_hsps, hsps, n * sizeof(sa_segment_pair), hipMemcpyHostToDevice, s), "hsp chain: HSPs");
     if (group) check_memcpy(hipMemcpyAsync(d_group, group, n * sizeof(uint32_t), hipMemcpyHostToDevice, s), "hsp chain: groups");
+    if (costs.on) check_memcpy(hipMemcpyAsync(sl->hspcost_image.p, costs.w, sizeof(costs.w), hipMemcpyHostToDevice, s), "hsp chain: gap costs");
 
     // rank: stable sort by (query_start, len) with the input index as value, then by (group, ref_start); idx_a ends up as rank -> input index
     std::vector<uint32_t> h_first(tiles);
@@ -100,12 +153,14 @@ void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, u
             exit(15);
         }
         if (b > c0) {
-            ProfScope ps(sl, "hspchain_cross");
-            launch_hspchain_cross(a, b, c0, partial, s);
+            ProfScope ps(sl, costs.on ? "hspcost_cross" : "hspchain_cross");
+            if (costs.on) launch_hspcost_cross(ca, b, c0, partial, s);
+            else launch_hspchain_cross(a, b, c0, partial, s);
         }
         {
-            ProfScope ps(sl, "hspchain_resolve");
-            launch_hspchain_resolve(a, b, c0, partial, s);
+            ProfScope ps(sl, costs.on ? "hspcost_resolve" : "hspchain_resolve");
+            if (costs.on) launch_hspcost_resolve(ca, b, c0, partial, s);
+            else launch_hspchain_resolve(a, b, c0, partial, s);
         }
         check_launch("hspchain tile");
         st.pair_evals += (uint64_t)(b - c0) * T * nb + (uint64_t)nb * (nb - 1) / 2;
@@ -130,12 +185,8 @@ uint32_t checked(const sa_chain_params* p, size_t n, sa_chain_params& P) {
     return (uint32_t)tile_opt;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t sa_chain_hsps(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p, sa_chain_member** members,
-                     sa_chain_node** nodes, sa_chain_stats* stats) {
+size_t chain_hsps(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p, const sa_chain_gap_costs* g,
+                  sa_chain_member** members, sa_chain_node** nodes, sa_chain_stats* stats) {
     *members = nullptr;
     if (nodes) *nodes = nullptr;
     sa_chain_stats st;
@@ -144,11 +195,13 @@ size_t sa_chain_hsps(const sa_segment_pair* hsps, size_t n, const uint32_t* grou
     require_init("ChainHsps");
     ChainDp d;
     const uint32_t T = checked(p, n, d.P);
+    CostImage costs;
+    checked_costs(g, costs);
     if (n == 0) return 0;
     Slot* sl = d.sl = acquire_slot_early();
     hipStream_t s = sl->stream;
     ChainTimer ev(s, "hsp chain timing");
-    rank_and_dp(hsps, n, group, T, d, ev, st);
+    rank_and_dp(hsps, n, group, T, costs, d, ev, st);
     const uint32_t G = d.G;
 
     // finish: every group's end and chain length, then the members and the nodes
@@ -188,14 +241,9 @@ size_t sa_chain_hsps(const sa_segment_pair* hsps, size_t n, const uint32_t* grou
     return (size_t)total;
 }
 
-void sa_free_chain(sa_chain_member* members, sa_chain_node* nodes) {
-    free(members);
-    free(nodes);
-}
-
-size_t sa_chain_hsps_all(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p, sa_chain_record** chains,
-                         size_t* n_chains, sa_chain_all_member** members, sa_chain_node** nodes, uint32_t** chain_of,
-                         sa_chain_all_stats* stats) {
+size_t chain_hsps_all(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p, const sa_chain_gap_costs* g,
+                      sa_chain_record** chains, size_t* n_chains, sa_chain_all_member** members, sa_chain_node** nodes, uint32_t** chain_of,
+                      sa_chain_all_stats* stats) {
     *chains = nullptr;
     *n_chains = 0;
     *members = nullptr;
@@ -207,11 +255,13 @@ size_t sa_chain_hsps_all(const sa_segment_pair* hsps, size_t n, const uint32_t* 
     require_init("ChainHsps");
     ChainDp d;
     const uint32_t T = checked(p, n, d.P);
+    CostImage costs;
+    checked_costs(g, costs);
     if (n == 0) return 0;
     Slot* sl = d.sl = acquire_slot_early();
     hipStream_t s = sl->stream;
     ChainTimer ev(s, "hsp chain timing");
-    rank_and_dp(hsps, n, group, T, d, ev, st.chain);
+    rank_and_dp(hsps, n, group, T, costs, d, ev, st.chain);
     const uint32_t N = d.N;
 
     HspPeelArgs a;
@@ -299,6 +349,57 @@ size_t sa_chain_hsps_all(const sa_segment_pair* hsps, size_t n, const uint32_t* 
     if (nodes) *nodes = n_out;
     if (chain_of) *chain_of = o_out;
     return M;
+}
+
+// The two tables axtChain's usage text prints for -linearGap; q_gap = t_gap in both.
+const uint32_t PRESET_POS[11] = {1, 2, 3, 11, 111, 2111, 12111, 32111, 72111, 152111, 252111};
+const int64_t PRESET_LOOSE[2][11] = {{325, 360, 400, 450, 600, 1100, 3600, 7600, 15600, 31600, 56600},
+                                     {625, 660, 700, 750, 900, 1400, 4000, 8000, 16000, 32000, 57000}};
+const int64_t PRESET_MEDIUM[2][11] = {{350, 425, 450, 600, 900, 2900, 22900, 57900, 117900, 217900, 317900},
+                                      {750, 825, 850, 1000, 1300, 3300, 23300, 58300, 118300, 218300, 318300}};
+
+}  // namespace
+
+extern "C" {
+
+size_t sa_chain_hsps(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p, sa_chain_member** members,
+                     sa_chain_node** nodes, sa_chain_stats* stats) {
+    return chain_hsps(hsps, n, group, p, nullptr, members, nodes, stats);
+}
+
+size_t sa_chain_hsps_costs(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p,
+                           const sa_chain_gap_costs* g, sa_chain_member** members, sa_chain_node** nodes, sa_chain_stats* stats) {
+    return chain_hsps(hsps, n, group, p, g, members, nodes, stats);
+}
+
+void sa_free_chain(sa_chain_member* members, sa_chain_node* nodes) {
+    free(members);
+    free(nodes);
+}
+
+size_t sa_chain_hsps_all(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p, sa_chain_record** chains,
+                         size_t* n_chains, sa_chain_all_member** members, sa_chain_node** nodes, uint32_t** chain_of,
+                         sa_chain_all_stats* stats) {
+    return chain_hsps_all(hsps, n, group, p, nullptr, chains, n_chains, members, nodes, chain_of, stats);
+}
+
+size_t sa_chain_hsps_all_costs(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p,
+                               const sa_chain_gap_costs* g, sa_chain_record** chains, size_t* n_chains, sa_chain_all_member** members,
+                               sa_chain_node** nodes, uint32_t** chain_of, sa_chain_all_stats* stats) {
+    return chain_hsps_all(hsps, n, group, p, g, chains, n_chains, members, nodes, chain_of, stats);
+}
+
+int sa_chain_gap_preset(const char* name, sa_chain_gap_costs* out) {
+    const int64_t (*t)[11] = !name ? nullptr : !strcmp(name, "loose") ? PRESET_LOOSE : !strcmp(name, "medium") ? PRESET_MEDIUM : nullptr;
+    if (!t || !out) return -1;
+    memset(out, 0, sizeof(*out));
+    out->n = 11;
+    for (int k = 0; k < 11; k++) {
+        out->pos[k] = PRESET_POS[k];
+        out->q_gap[k] = out->t_gap[k] = t[0][k];
+        out->both_gap[k] = t[1][k];
+    }
+    return 0;
 }
 
 void sa_free_chain_all(sa_chain_record* chains, sa_chain_all_member* members, sa_chain_node* nodes, uint32_t* chain_of) {

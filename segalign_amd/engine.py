@@ -41,6 +41,7 @@ C_ABI_SYMBOLS = [
     "sa_seed_calls", "sa_count_call_hits", "sa_count_chunk_hits", "sa_get_wga_chunk", "sa_release_arena", "sa_set_option", "sa_reset_option", "sa_get_option", "sa_option_count", "sa_option_name", "sa_get_audit",
     "sa_gapped_extend", "sa_free_gapped", "sa_gapped_align", "sa_free_gapped_align", "sa_gapped_align_greedy",
     "sa_chain_hsps", "sa_free_chain", "sa_chain_hsps_all", "sa_free_chain_all",
+    "sa_chain_hsps_costs", "sa_chain_hsps_all_costs", "sa_chain_gap_preset",
     "sa_stitch_chains", "sa_free_stitch",
     "sa_net_chains", "sa_free_net",
 ]
@@ -89,6 +90,14 @@ CHAIN_NONE = 0xFFFFFFFF  # chain_of of a member of a chain dropped by min_score
 
 class ChainParams(C.Structure):
     _fields_ = [("diag_pen", C.c_int32), ("anti_pen", C.c_int32), ("max_gap", C.c_uint32), ("pad", C.c_uint32), ("min_score", C.c_int64)]
+
+
+CHAIN_GAP_POINTS = 16
+
+
+class ChainGapCosts(C.Structure):  # sa_chain_gap_costs
+    _fields_ = [("n", C.c_uint32), ("pad", C.c_uint32), ("pos", C.c_uint32 * CHAIN_GAP_POINTS), ("q_gap", C.c_int64 * CHAIN_GAP_POINTS),
+                ("t_gap", C.c_int64 * CHAIN_GAP_POINTS), ("both_gap", C.c_int64 * CHAIN_GAP_POINTS)]
 
 
 class ChainStats(C.Structure):
@@ -247,6 +256,15 @@ def lib():
     L.sa_chain_hsps_all.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(ChainParams), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                     C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(ChainAllStats)]
     L.sa_free_chain_all.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sa_chain_hsps_costs.restype = C.c_size_t
+    L.sa_chain_hsps_costs.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(ChainParams), C.POINTER(ChainGapCosts),
+                                      C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(ChainStats)]
+    L.sa_chain_hsps_all_costs.restype = C.c_size_t
+    L.sa_chain_hsps_all_costs.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(ChainParams), C.POINTER(ChainGapCosts),
+                                          C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                          C.POINTER(C.c_void_p), C.POINTER(ChainAllStats)]
+    L.sa_chain_gap_preset.restype = C.c_int
+    L.sa_chain_gap_preset.argtypes = [C.c_char_p, C.POINTER(ChainGapCosts)]
     L.sa_stitch_chains.restype = C.c_size_t
     L.sa_stitch_chains.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(StitchParams),
                                    C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
@@ -527,29 +545,92 @@ def _chain_take(ptr, count, dtype):
     return np.frombuffer((C.c_char * (count * dtype.itemsize)).from_address(ptr.value), dtype=dtype).copy()
 
 
-def ChainHsps(hsps, groups=None, diag_pen=0, anti_pen=0, max_gap=0, min_score=0, nodes=False):
+def chain_gap_costs(table):
+    """A gap-cost table for ChainHsps / ChainHspsAll (sa_chain_gap_costs; contract in include/segalign_amd.h).
+    table: "loose" or "medium" (the presets of sa_chain_gap_preset), a dict {"pos", "q_gap", "t_gap", "both_gap"} of equally long
+    sequences (1 .. 16 break points), or a ChainGapCosts, which is returned as it is.  The values are checked by the entry, not here."""
+    if isinstance(table, ChainGapCosts):
+        return table
+    t = ChainGapCosts()
+    if isinstance(table, str):
+        if lib().sa_chain_gap_preset(table.encode(), C.byref(t)) != 0:
+            raise ValueError("chain_gap_costs: no preset %r (loose, medium)" % table)
+        return t
+    cols = [list(table[k]) for k in ("pos", "q_gap", "t_gap", "both_gap")]
+    n = len(cols[0])
+    if any(len(c) != n for c in cols):
+        raise ValueError("chain_gap_costs: pos, q_gap, t_gap and both_gap must be equally long")
+    if n > CHAIN_GAP_POINTS:
+        raise ValueError("chain_gap_costs: at most %d break points" % CHAIN_GAP_POINTS)
+    t.n = n
+    for k in range(n):
+        t.pos[k], t.q_gap[k], t.t_gap[k], t.both_gap[k] = (int(c[k]) for c in cols)
+    return t
+
+
+def parse_linear_gap(text):
+    """A gap-cost table in axtChain's -linearGap file layout, as segalign_host --gpu_chain_costs=FILE reads it: lines `tableSize N`,
+    `smallSize N` (read and ignored), then `position`, `qGap`, `tGap` and `bothGap` with tableSize integers each; blank lines and lines
+    starting with # are skipped.  -> the dict chain_gap_costs takes.  ValueError for anything else."""
+    want = {"tableSize": None, "smallSize": None, "position": None, "qGap": None, "tGap": None, "bothGap": None}
+    for line in text.splitlines():
+        w = line.split()
+        if not w or w[0].startswith("#"):
+            continue
+        if w[0] not in want or want[w[0]] is not None:
+            raise ValueError("linearGap: unknown or repeated line %r" % w[0])
+        try:
+            want[w[0]] = [int(x) for x in w[1:]]
+        except ValueError:
+            raise ValueError("linearGap: %s: not an integer" % w[0])
+    for k in ("tableSize", "position", "qGap", "tGap", "bothGap"):
+        if want[k] is None:
+            raise ValueError("linearGap: no %s line" % k)
+    if len(want["tableSize"]) != 1 or (want["smallSize"] is not None and len(want["smallSize"]) != 1):
+        raise ValueError("linearGap: tableSize and smallSize take one value")
+    n = want["tableSize"][0]
+    if not 1 <= n <= CHAIN_GAP_POINTS:
+        raise ValueError("linearGap: tableSize %d is not in 1 .. %d" % (n, CHAIN_GAP_POINTS))
+    for k in ("position", "qGap", "tGap", "bothGap"):
+        if len(want[k]) != n:
+            raise ValueError("linearGap: %s has %d values, tableSize is %d" % (k, len(want[k]), n))
+    return {"pos": want["position"], "q_gap": want["qGap"], "t_gap": want["tGap"], "both_gap": want["bothGap"]}
+
+
+def ChainHsps(hsps, groups=None, diag_pen=0, anti_pen=0, max_gap=0, min_score=0, nodes=False, gap_costs=None):
     """The best collinear chain of every group of HSPs (sa_chain_hsps; contract in include/segalign_amd.h).
     hsps: SEG_DTYPE records; groups: one uint32 per HSP (None: all in group 0).  -> (CHAIN_MEMBER_DTYPE members, stats dict), or with
-    nodes=True (members, CHAIN_NODE_DTYPE nodes in input order, stats dict).  Needs InitializeInterface only."""
+    nodes=True (members, CHAIN_NODE_DTYPE nodes in input order, stats dict).  gap_costs: what chain_gap_costs takes, for a link's
+    piecewise-linear gap cost on top of the linear terms (sa_chain_hsps_costs); None: none.  Needs InitializeInterface only."""
     h, g, p = _chain_input(hsps, groups, diag_pen, anti_pen, max_gap, min_score)
     mem, nod, st = C.c_void_p(), C.c_void_p(), ChainStats()
-    m = lib().sa_chain_hsps(h.ctypes.data if h.size else None, h.size, g.ctypes.data if g is not None and g.size else None, C.byref(p),
-                            C.byref(mem), C.byref(nod) if nodes else None, C.byref(st))
+    if gap_costs is not None:
+        m = lib().sa_chain_hsps_costs(h.ctypes.data if h.size else None, h.size, g.ctypes.data if g is not None and g.size else None,
+                                      C.byref(p), C.byref(chain_gap_costs(gap_costs)), C.byref(mem), C.byref(nod) if nodes else None,
+                                      C.byref(st))
+    else:
+        m = lib().sa_chain_hsps(h.ctypes.data if h.size else None, h.size, g.ctypes.data if g is not None and g.size else None, C.byref(p),
+                                C.byref(mem), C.byref(nod) if nodes else None, C.byref(st))
     res_m, res_n = _chain_take(mem, m, CHAIN_MEMBER_DTYPE), _chain_take(nod, h.size, CHAIN_NODE_DTYPE)
     lib().sa_free_chain(mem, nod)
     return (res_m, res_n, _flat(st)) if nodes else (res_m, _flat(st))
 
 
-def ChainHspsAll(hsps, groups=None, diag_pen=0, anti_pen=0, max_gap=0, min_score=0, nodes=False):
+def ChainHspsAll(hsps, groups=None, diag_pen=0, anti_pen=0, max_gap=0, min_score=0, nodes=False, gap_costs=None):
     """All collinear chains of every group of HSPs, peeled best first (sa_chain_hsps_all; contract in include/segalign_amd.h,
     DESIGN.md 16).  Arguments as ChainHsps.  -> (CHAIN_RECORD_DTYPE chains, CHAIN_ALL_MEMBER_DTYPE members, uint32 chain_of in input
     order (CHAIN_NONE: the HSP's chain scores below min_score), stats dict); with nodes=True the CHAIN_NODE_DTYPE nodes come before
-    chain_of.  Needs InitializeInterface only."""
+    chain_of.  gap_costs as for ChainHsps (sa_chain_hsps_all_costs).  Needs InitializeInterface only."""
     h, g, p = _chain_input(hsps, groups, diag_pen, anti_pen, max_gap, min_score)
     ch, mem, nod, cof, st, nc = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), ChainAllStats(), C.c_size_t(0)
-    m = lib().sa_chain_hsps_all(h.ctypes.data if h.size else None, h.size, g.ctypes.data if g is not None and g.size else None,
-                                C.byref(p), C.byref(ch), C.byref(nc), C.byref(mem), C.byref(nod) if nodes else None, C.byref(cof),
-                                C.byref(st))
+    if gap_costs is not None:
+        m = lib().sa_chain_hsps_all_costs(h.ctypes.data if h.size else None, h.size, g.ctypes.data if g is not None and g.size else None,
+                                          C.byref(p), C.byref(chain_gap_costs(gap_costs)), C.byref(ch), C.byref(nc), C.byref(mem),
+                                          C.byref(nod) if nodes else None, C.byref(cof), C.byref(st))
+    else:
+        m = lib().sa_chain_hsps_all(h.ctypes.data if h.size else None, h.size, g.ctypes.data if g is not None and g.size else None,
+                                    C.byref(p), C.byref(ch), C.byref(nc), C.byref(mem), C.byref(nod) if nodes else None, C.byref(cof),
+                                    C.byref(st))
     res_c, res_m = _chain_take(ch, nc.value, CHAIN_RECORD_DTYPE), _chain_take(mem, m, CHAIN_ALL_MEMBER_DTYPE)
     res_n, res_o = _chain_take(nod, h.size, CHAIN_NODE_DTYPE), _chain_take(cof, h.size, np.uint32)
     lib().sa_free_chain_all(ch, mem, nod, cof)

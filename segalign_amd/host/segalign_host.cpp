@@ -49,6 +49,8 @@ struct Config {  // src/graph.h:32-76 with the defaults of src/main.cpp:61-124
     bool gpu_chain_all = false;  // --gpu_chain_all[=diag,anti]: a .chains file with all chains (sa_chain_hsps_all); the gapped entries get the kept chains' HSPs
     bool chain_min_set = false;
     long long chain_min = 0;  // --gpu_chain_min=N: sa_chain_params.min_score of --gpu_chain_all
+    bool chain_costs_set = false;  // --gpu_chain_costs=loose|medium|FILE (with --gpu_chain or --gpu_chain_all): a piecewise-linear gap cost per link
+    sa_chain_gap_costs chain_costs;  // (sa_chain_hsps_costs / sa_chain_hsps_all_costs)
     bool gpu_stitch = false;  // --gpu_stitch[=max_link] (with --gpu_chain or --gpu_chain_all): a .stitched.maf file next to every .chain / .chains file (sa_stitch_chains)
     uint32_t stitch_max_link = 0;  // sa_stitch_params.max_link; 0: the engine's default
     bool stitch_min_set = false;
@@ -275,7 +277,8 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
             std::vector<uint32_t> ctarget;
             if (cfg.gpu_chain) {
                 sa_chain_member* mem = nullptr;
-                const size_t nm = sa_chain_hsps(v.data(), v.size(), group.data(), &cp, &mem, nullptr, nullptr);
+                const size_t nm = cfg.chain_costs_set ? sa_chain_hsps_costs(v.data(), v.size(), group.data(), &cp, &cfg.chain_costs, &mem, nullptr, nullptr)
+                                                      : sa_chain_hsps(v.data(), v.size(), group.data(), &cp, &mem, nullptr, nullptr);
                 idx.resize(nm);
                 for (size_t k = 0; k < nm; k++) { emit(v[mem[k].hsp_index]); idx[k] = mem[k].hsp_index; }  // the order sa_chain_hsps returns, on both strands
                 for (size_t k = 1; k <= nm; k++)
@@ -285,7 +288,9 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
                 sa_chain_record* ch = nullptr;
                 sa_chain_all_member* mem = nullptr;
                 size_t nc = 0;
-                const size_t nm = sa_chain_hsps_all(v.data(), v.size(), group.data(), &cp, &ch, &nc, &mem, nullptr, nullptr, nullptr);
+                const size_t nm = cfg.chain_costs_set
+                    ? sa_chain_hsps_all_costs(v.data(), v.size(), group.data(), &cp, &cfg.chain_costs, &ch, &nc, &mem, nullptr, nullptr, nullptr)
+                    : sa_chain_hsps_all(v.data(), v.size(), group.data(), &cp, &ch, &nc, &mem, nullptr, nullptr, nullptr);
                 idx.resize(nm);
                 for (size_t c = 0; c < nc; c++) {  // the order sa_chain_hsps_all returns, on both strands
                     fprintf(f, "#chain %zu group=%u score=%lld members=%u joined=%d\n", c, ch[c].group, (long long)ch[c].score, ch[c].n_members,
@@ -458,6 +463,9 @@ static void usage() {
             "      every pair, peeled best first, each under a line '#chain k group=g score=s members=m joined=0|1'; takes --gpu_chain_gap and\n"
             "      the same limit; --gpu_gapped then extends the HSPs of the chains kept)\n"
             "  --gpu_chain_min=N (with --gpu_chain_all: chains that score less than N are not kept; default 0)\n"
+            "  --gpu_chain_costs=loose|medium|FILE (with --gpu_chain or --gpu_chain_all: a link also pays a piecewise-linear gap cost, in the\n"
+            "      spirit of axtChain -linearGap: its two preset tables, or a FILE in its layout with at most 16 break points: lines\n"
+            "      'tableSize N', 'smallSize N' (ignored), 'position ...', 'qGap ...', 'tGap ...', 'bothGap ...')\n"
             "  --gpu_stitch[=max_link] (with --gpu_chain or --gpu_chain_all: a .stitched.maf file next to each .chain / .chains file with every\n"
             "      chain as one alignment through all its members, the stretch between two members aligned globally with --gap=O,E; a chain\n"
             "      is cut where a side of that stretch exceeds max_link (default and at most 2048) or holds a record boundary)\n"
@@ -467,6 +475,51 @@ static void usage() {
             "      line 'net <target record> <length>' per record, then per fill, indented by its depth, 'fill <tstart> <tsize> <qname> <+|->\n"
             "      <qstart> <qsize> chain=<k> score=<s> ali=<n>'; open stretches shorter than min_space, default 1, are not searched)\n"
             "  --gpu_net_fill=N (with --gpu_net: a chain fills an open stretch only with at least N bases in it; default 1)\n");
+}
+
+// A gap-cost table in axtChain's linearGap layout (see usage).  The file's form is checked here; the values are checked again by the
+// chaining entry, so they are checked here too, to fail before any GPU work.  Returns false with a message in err.
+static bool read_linear_gap(const std::string& path, sa_chain_gap_costs& out, std::string& err) {
+    FILE* f = fopen(path.c_str(), "r");
+    if (!f) { err = "cannot open it"; return false; }
+    memset(&out, 0, sizeof(out));
+    const char* names[6] = {"tableSize", "smallSize", "position", "qGap", "tGap", "bothGap"};
+    std::vector<long long> vals[6];
+    bool seen[6] = {false, false, false, false, false, false};
+    char line[4096];
+    while (fgets(line, sizeof(line), f)) {
+        char* tok = strtok(line, " \t\r\n");
+        if (!tok || tok[0] == '#') continue;
+        int w = -1;
+        for (int k = 0; k < 6; k++) if (!strcmp(tok, names[k])) w = k;
+        if (w < 0 || seen[w]) { err = std::string("unknown or repeated line ") + tok; fclose(f); return false; }
+        seen[w] = true;
+        while ((tok = strtok(nullptr, " \t\r\n"))) {
+            char* endp = nullptr;
+            const long long x = strtoll(tok, &endp, 10);
+            if (endp == tok || *endp) { err = std::string(names[w]) + ": " + tok + " is not an integer"; fclose(f); return false; }
+            vals[w].push_back(x);
+        }
+    }
+    fclose(f);
+    for (int k = 0; k < 6; k++) if (k != 1 && !seen[k]) { err = std::string("no ") + names[k] + " line"; return false; }
+    if (vals[0].size() != 1 || (seen[1] && vals[1].size() != 1)) { err = "tableSize and smallSize take one value"; return false; }
+    const long long n = vals[0][0];
+    if (n < 1 || n > SA_CHAIN_GAP_POINTS) { err = "tableSize is not in 1 .. 16"; return false; }
+    for (int k = 2; k < 6; k++) if ((long long)vals[k].size() != n) { err = std::string(names[k]) + " does not have tableSize values"; return false; }
+    out.n = (uint32_t)n;
+    int64_t* cost[3] = {out.q_gap, out.t_gap, out.both_gap};
+    for (long long k = 0; k < n; k++) {
+        if (vals[2][k] < 1 || vals[2][k] > 0xffffffffll || (k > 0 && vals[2][k] <= vals[2][k - 1])) { err = "position must ascend strictly from at least 1"; return false; }
+        out.pos[k] = (uint32_t)vals[2][k];
+        for (int a = 0; a < 3; a++) {
+            const long long c = vals[3 + a][k];
+            if (c < 0 || c > (1ll << 40) || (k > 0 && c < vals[3 + a][k - 1])) { err = std::string(names[3 + a]) + " must be non-decreasing within 0 .. 2^40"; return false; }
+            if (k > 0 && ((c - vals[3 + a][k - 1]) << 16) / (vals[2][k] - vals[2][k - 1]) >= (1ll << 27)) { err = std::string(names[3 + a]) + " rises by 2048 or more per base"; return false; }
+            cost[a][k] = c;
+        }
+    }
+    return true;
 }
 
 int main(int argc, char** argv) {
@@ -533,6 +586,14 @@ int main(int argc, char** argv) {
             if (endp == v.c_str() || *endp || gap < 0 || gap > 0xffffffffll) { fprintf(stderr, "bad --gpu_chain_gap=%s (0 .. 4294967295; 0: unlimited)\n", v.c_str()); return 1; }
             cfg.chain_gap = (uint32_t)gap;
         }
+        else if (opt(a, "--gpu_chain_costs", v)) {
+            std::string err;
+            if (sa_chain_gap_preset(v.c_str(), &cfg.chain_costs) != 0 && !read_linear_gap(v, cfg.chain_costs, err)) {
+                fprintf(stderr, "bad --gpu_chain_costs=%s (loose, medium or a linearGap file): %s\n", v.c_str(), err.c_str());
+                return 1;
+            }
+            cfg.chain_costs_set = true;
+        }
         else if (!strcmp(a, "--gpu_stitch")) cfg.gpu_stitch = true;
         else if (opt(a, "--gpu_stitch", v)) {
             char* endp = nullptr;
@@ -575,6 +636,7 @@ int main(int argc, char** argv) {
     }
     if (cfg.gpu_chain && cfg.gpu_chain_all) { fprintf(stderr, "--gpu_chain and --gpu_chain_all exclude each other\n"); return 1; }
     if (cfg.chain_min_set && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_chain_min needs --gpu_chain_all\n"); return 1; }
+    if (cfg.chain_costs_set && !cfg.gpu_chain && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_chain_costs needs --gpu_chain or --gpu_chain_all\n"); return 1; }
     if (cfg.gpu_stitch && !cfg.gpu_chain && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_stitch needs --gpu_chain or --gpu_chain_all\n"); return 1; }
     if (cfg.stitch_min_set && !cfg.gpu_stitch) { fprintf(stderr, "--gpu_stitch_min needs --gpu_stitch\n"); return 1; }
     if (cfg.gpu_net && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_net needs --gpu_chain_all\n"); return 1; }

@@ -14,6 +14,11 @@ members kept, pair evaluations, tile steps, the chain kernel ms and pair evaluat
 --greedy also the alignment / greedy) times on the chain's members beside those on all HSPs.  f and pred of every HSP and the members
 are checked against the numpy model (tests/hsp_chain_model.py) once per run.
 
+With --chain-costs loose|medium|FILE (with --chain) the same HSPs also go through sa_chain_hsps_costs under that gap-cost
+table (FILE: axtChain's linearGap layout) on top of --chain-pen, in runs that alternate with the linear ones: the line then adds the
+chain kernel ms and pair evaluations per second of the table runs beside the linear ones, every run's kernel ms, their ratio, and the
+members and score under the table.  f, pred and the members are checked against tests/hsp_chain_gap_model.py once per run.
+
 With --chain-all [--chain-min N] (which implies --chain) the HSPs also go through sa_chain_hsps_all: the line then adds
 the chains before min_score, the chains, joined chains and members kept, the doubling rounds, peel ms beside the DP's kernel ms, and
 the gapped times on the kept chains' members beside those on the best chain and on all HSPs.  The chains, members and chain_of are
@@ -29,7 +34,7 @@ With --net [--net-space N] [--net-fill N] (which implies --chain-all) the kept c
 net ms beside peel ms and the DP's kernel ms.  The fills are checked against the model (tests/net_model.py) once per run.
 
   python tools/gapped_bench.py [--workloads standin,lumpy] [--repeat 3] [--align] [--greedy] [--batches 1024,2048,...]
-                               [--pieces N] [--max-extent M] [--chain] [--chain-pen D,A] [--chain-all] [--chain-min N] [--stitch] [--stitch-max-link N]
+                               [--pieces N] [--max-extent M] [--chain] [--chain-pen D,A] [--chain-costs T] [--chain-all] [--chain-min N] [--stitch] [--stitch-max-link N]
                                [--net] [--net-space N] [--net-fill N]
 """
 import argparse
@@ -254,18 +259,48 @@ def chain_all_fields(hsps, repeat, pen, min_score, dp, align, greedy, stitch=Non
     return out
 
 
-def chain_fields(hsps, repeat, pen, align, greedy, all_min=None, stitch=None, net=None):
+def chain_costs_table(name):
+    """--chain-costs: a preset's name or a linearGap file -> what engine.chain_gap_costs takes."""
+    if name in ("loose", "medium"):
+        return name
+    with open(name) as f:
+        return E.parse_linear_gap(f.read())
+
+
+def chain_costs_fields(hsps, pen, costs, runs, linear_ms):
+    """The runs of sa_chain_hsps_costs that chain_fields interleaved with the linear ones, checked against the model."""
+    import hsp_chain_gap_model as GM
+    members, nodes, st = min(runs, key=lambda r: r[2]["kernel_ms"])
+    t0 = time.perf_counter()
+    f, pred, want = GM.chain(hsps, None, diag_pen=pen[0], anti_pen=pen[1], gap_costs=chain_costs_table(costs))
+    model_s = time.perf_counter() - t0
+    if not (np.array_equal(nodes["f"], f) and np.array_equal(nodes["pred"], pred) and np.array_equal(members, want)):
+        raise SystemExit("sa_chain_hsps_costs differs from the model")
+    ms = st["kernel_ms"]
+    return {"chain_costs": costs, "chain_costs_members": int(st["members"]), "chain_costs_score": int(members["f"][-1]) if members.size else None,
+            "chain_costs_pair_evals": int(st["pair_evals"]), "chain_costs_kernel_ms": round(ms, 3),
+            "chain_costs_gpairs_per_s": round(st["pair_evals"] / (ms * 1e-3) / 1e9, 3) if ms > 0 else None,
+            "chain_costs_runs_ms": [round(r[2]["kernel_ms"], 3) for r in runs], "chain_linear_runs_ms": [round(x, 3) for x in linear_ms],
+            "chain_costs_over_linear": round(ms / min(linear_ms), 3) if min(linear_ms) > 0 else None,
+            "chain_costs_model_checked": True, "chain_costs_model_s": round(model_s, 1)}
+
+
+def chain_fields(hsps, repeat, pen, align, greedy, all_min=None, stitch=None, net=None, costs=None):
     """sa_chain_hsps on the HSPs as one group, checked against the numpy model, and the gapped entries on the chain's members; with
-    all_min also chain_all_fields."""
+    all_min also chain_all_fields, with costs also chain_costs_fields (its runs alternate with the linear ones)."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import hsp_chain_model as M
-    best = None
+    best, cost_runs, linear_ms = None, [], []
+    table = E.chain_gap_costs(chain_costs_table(costs)) if costs else None
     for _ in range(repeat):
         t0 = time.perf_counter()
         r = E.ChainHsps(hsps, None, diag_pen=pen[0], anti_pen=pen[1], nodes=True)
         wall = (time.perf_counter() - t0) * 1e3
+        linear_ms.append(r[2]["kernel_ms"])
         if best is None or r[2]["kernel_ms"] < best[0][2]["kernel_ms"]:
             best = (r, wall)
+        if table is not None:
+            cost_runs.append(E.ChainHsps(hsps, None, diag_pen=pen[0], anti_pen=pen[1], nodes=True, gap_costs=table))
     (members, nodes, st), wall = best
     t0 = time.perf_counter()
     f, pred, want = M.chain(hsps, None, diag_pen=pen[0], anti_pen=pen[1])
@@ -278,13 +313,15 @@ def chain_fields(hsps, repeat, pen, align, greedy, all_min=None, stitch=None, ne
            "chain_tile_steps": int(st["tile_steps"]), "chain_tile": int(E.get_option("chain_tile")), "chain_kernel_ms": round(st["kernel_ms"], 3),
            "chain_call_ms": round(wall, 3), "chain_gpairs_per_s": round(st["pair_evals"] / (st["kernel_ms"] * 1e-3) / 1e9, 3) if st["kernel_ms"] > 0 else None,
            "chain_model_checked": True, "chain_model_s": round(model_s, 1)}
+    if costs:
+        out.update(chain_costs_fields(hsps, pen, costs, cost_runs, linear_ms))
     out.update(kept_fields(kept, repeat, align, greedy, "kept_"))
     if all_min is not None:
         out.update(chain_all_fields(hsps, repeat, pen, all_min, (f, pred), align, greedy, stitch, net))
     return out
 
 
-def run(name, repeat, align=False, greedy=False, with_sel=True, pieces=0, chain=None, chain_all_min=None, stitch=None, net=None):
+def run(name, repeat, align=False, greedy=False, with_sel=True, pieces=0, chain=None, chain_all_min=None, stitch=None, net=None, chain_costs=None):
     t, q = workload(name)
     if greedy or pieces:
         E.set_option("debug", 1)  # sa_gapped_align_greedy then prints its edge count, the continuation its pieces
@@ -332,7 +369,7 @@ def run(name, repeat, align=False, greedy=False, with_sel=True, pieces=0, chain=
     if greedy:
         extra.update(greedy_fields(hsps, repeat, with_sel))
     if chain is not None:
-        extra.update(chain_fields(hsps, repeat, chain, align, greedy, chain_all_min, stitch, net))
+        extra.update(chain_fields(hsps, repeat, chain, align, greedy, chain_all_min, stitch, net, chain_costs))
     E.ShutdownProcessor()
     if greedy or pieces:
         E.reset_option("debug")
@@ -356,6 +393,7 @@ def main():
     ap.add_argument("--max-extent", type=int, default=0, help="max_extent of every entry (0: the default, 65536)")
     ap.add_argument("--chain", action="store_true", help="also chain the HSPs (sa_chain_hsps) and time the gapped entries on the chain's members")
     ap.add_argument("--chain-pen", default="0,0", help="with --chain: diag_pen,anti_pen")
+    ap.add_argument("--chain-costs", default="", help="with --chain: also chain under this gap-cost table (loose, medium or a linearGap file)")
     ap.add_argument("--chain-all", action="store_true", help="also peel the HSPs into all chains (sa_chain_hsps_all); implies --chain")
     ap.add_argument("--chain-min", type=int, default=0, help="with --chain-all: min_score")
     ap.add_argument("--stitch", action="store_true", help="also stitch the kept chains (sa_stitch_chains); implies --chain-all")
@@ -366,12 +404,15 @@ def main():
     a = ap.parse_args()
     a.chain_all = a.chain_all or a.stitch or a.net
     chain = tuple(int(x) for x in a.chain_pen.split(",")) if a.chain or a.chain_all else None
+    if a.chain_costs and chain is None:
+        ap.error("--chain-costs needs --chain")
     if a.max_extent:
         KW["max_extent"] = a.max_extent
     for name in a.workloads.split(","):
         if not a.batches:
             print(json.dumps(run(name, a.repeat, a.align, a.greedy, pieces=a.pieces, chain=chain, chain_all_min=a.chain_min if a.chain_all else None,
-                                 stitch=a.stitch_max_link if a.stitch else None, net=(a.net_space, a.net_fill) if a.net else None)), flush=True)
+                                 stitch=a.stitch_max_link if a.stitch else None, net=(a.net_space, a.net_fill) if a.net else None,
+                                 chain_costs=a.chain_costs or None)), flush=True)
             continue
         for b in a.batches.split(","):
             E.set_option("gapped_greedy_batch", int(b))
