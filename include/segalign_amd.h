@@ -308,6 +308,33 @@ int sa_get_filter_mode(void);
 int sa_get_lookup_mode(void);
 uint64_t sa_get_neighbourhood_entries(void); /* run entries of the neighbourhood table (0 when not built) */
 
+/* Test entries (read-only; tests/test_gpu_table_regimes.py, DESIGN.md 4.2''): how the resident tables of device 0 were made, and
+ * the neighbourhood table itself. */
+#define SA_TABLE_BUILD_NONE 0            /* no table */
+#define SA_TABLE_BUILD_TWO_LEVEL 1       /* partition build, keys of up to 24 bits */
+#define SA_TABLE_BUILD_THREE_LEVEL 2     /* partition build with the third level (keys above 24 bits) */
+#define SA_TABLE_BUILD_ATOMIC 3          /* atomic build: by seed weight, by device, or by option table_atomic */
+#define SA_TABLE_BUILD_ATOMIC_GAVE_UP 4  /* atomic build after the three-level partition build gave up on this table */
+#define SA_NBR_FILL_NONE 0               /* no neighbourhood table (not built yet, or not available) */
+#define SA_NBR_FILL_ALIAS 1              /* no transition word and no context: the runs ARE pos_table */
+#define SA_NBR_FILL_POSITIONS 2          /* positions only (lookup mode 1) */
+#define SA_NBR_FILL_CTX_ONE_STAGE 3      /* context records, every entry cuts its own */
+#define SA_NBR_FILL_CTX_DENSE 4          /* context records, two stages, a wave per key */
+#define SA_NBR_FILL_CTX_SPARSE 5         /* context records, two stages, a lane per key */
+typedef struct sa_table_build_info {
+    int32_t build;                /* SA_TABLE_BUILD_* */
+    uint32_t unsorted_partitions; /* partitions the finish kernel of the partition build could not hold in LDS (0 for an atomic build) */
+    int32_t nbr_fill;             /* SA_NBR_FILL_* */
+    uint32_t left_skip;           /* what the context records were cut with: seed_size, or 0 (option ctx_skip_seed = 0); 0 without records */
+} sa_table_build_info;
+int sa_get_table_build_info(sa_table_build_info* out); /* 0; -1 (and *out zeroed) before sa_initialize_interface */
+/* nbr_start[first_key .. first_key + count) of device `dev`; keys run to 4^kmer_size INCLUSIVE (the last word is the number of
+ * entries).  0, or -1 with a message on stderr when the table is not built or the range leaves it: nothing is copied then. */
+int sa_copy_neighbourhood_starts(int dev, uint64_t first_key, uint64_t count, uint64_t* dst);
+/* entries [first_entry, first_entry + count) of the neighbourhood table: 32-byte context records {pos, w[7]} in lookup mode 2,
+ * uint32 seed start positions in mode 1.  Returns which (2 or 1), or -1 with a message as above. */
+int sa_copy_neighbourhood_records(int dev, uint64_t first_entry, uint64_t count, void* dst);
+
 /* Per-kernel HIP-event timing on the engine's own streams (bench.py's roofline leg). */
 void sa_profile_enable(int on);
 void sa_profile_reset(void);

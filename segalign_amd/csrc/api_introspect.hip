@@ -54,6 +54,60 @@ void sa_copy_query_codes(int dev, uint32_t buffer, int rev, uint8_t* dst) {
     check_memcpy(hipMemcpy(dst, b.codes, b.len, hipMemcpyDeviceToHost), "query codes");
 }
 
+// ---- the tables as they were built (tests/test_gpu_table_regimes.py, DESIGN.md 4.2'') ---------------------------------------------------
+// What sa_generate_seed_pos_table and ensure_nbr recorded about device 0: which build, how many partitions the finish kernel left to the
+// global sort, which neighbourhood fill.  Read-only; builds nothing (sa_get_lookup_mode does).
+int sa_get_table_build_info(sa_table_build_info* o) {
+    memset(o, 0, sizeof(*o));
+    if (g_ndev <= 0) return -1;
+    DevCtx* dc = g_dev[0];
+    std::lock_guard<std::mutex> lk(dc->nbr_mu);
+    o->build = dc->pos_table ? dc->table_build : SA_TABLE_BUILD_NONE;
+    o->unsorted_partitions = dc->pos_table ? dc->table_unsorted : 0u;
+    o->nbr_fill = dc->nbr_state == 1 ? dc->nbr_fill : SA_NBR_FILL_NONE;
+    o->left_skip = (dc->nbr_state == 1 && dc->nbr_ctx) ? dc->nbr_left_skip : 0u;
+    return 0;
+}
+// a range of the neighbourhood table of device `dev`, or nullptr with a message: not built, or the range leaves it
+static DevCtx* nbr_range(int dev, uint64_t first, uint64_t count, bool starts, const char* what) {
+    if (dev < 0 || dev >= g_ndev) {
+        fprintf(stderr, "Error: %s: device %d out of range\n", what, dev);
+        return nullptr;
+    }
+    DevCtx* dc = g_dev[dev];
+    const bool have = dc->nbr_state == 1 && dc->nbr_start && (dc->nbr_ctx || dc->nbr_pos || dc->nbr_total == 0);
+    if (!have) {
+        fprintf(stderr, "Error: %s: the neighbourhood table of device %d is not built\n", what, dev);
+        return nullptr;
+    }
+    const uint64_t limit = starts ? (uint64_t)dc->nkeys + 1 : dc->nbr_total;
+    if (first > limit || count > limit - first) {
+        fprintf(stderr, "Error: %s: [%llu, +%llu) leaves the table's %llu\n", what, (unsigned long long)first, (unsigned long long)count,
+                (unsigned long long)limit);
+        return nullptr;
+    }
+    check_set_device(dc->dev, "copy");
+    return dc;
+}
+int sa_copy_neighbourhood_starts(int dev, uint64_t first_key, uint64_t count, uint64_t* dst) {
+    DevCtx* dc = nbr_range(dev, first_key, count, true, "sa_copy_neighbourhood_starts");
+    if (!dc) return -1;
+    std::lock_guard<std::mutex> lk(dc->nbr_mu);
+    if (count) check_memcpy(hipMemcpy(dst, dc->nbr_start + first_key, count * sizeof(uint64_t), hipMemcpyDeviceToHost), "neighbourhood starts");
+    return 0;
+}
+int sa_copy_neighbourhood_records(int dev, uint64_t first_entry, uint64_t count, void* dst) {
+    DevCtx* dc = nbr_range(dev, first_entry, count, false, "sa_copy_neighbourhood_records");
+    if (!dc) return -1;
+    std::lock_guard<std::mutex> lk(dc->nbr_mu);
+    if (dc->nbr_ctx) {
+        if (count) check_memcpy(hipMemcpy(dst, dc->nbr_ctx + first_entry, count * sizeof(CtxRec), hipMemcpyDeviceToHost), "neighbourhood records");
+        return 2;
+    }
+    if (count) check_memcpy(hipMemcpy(dst, dc->nbr_pos + first_entry, count * sizeof(uint32_t), hipMemcpyDeviceToHost), "neighbourhood positions");
+    return 1;
+}
+
 // The ordering stage alone (dedup.hip) on records the host hands in, as ONE dedup scope: what the reference does to the anchors of an
 // iteration -- stable_sort(hspComp) -> unique_copy(hspEqual) -> stable_sort(hspCompLastz), src/seed_filter.cu:776-782; rm != 0: the
 // repeat masker's chain, repeat_masker_src/seed_filter.cu:819-831.  path 0: the per-segment LDS chain (dedup_seg_kernel; plain

@@ -222,6 +222,8 @@ static void release_device_state(DevCtx* dc) {
     dc->keep_pos.release("d_pos_table");
     dc->keep_nbr_start.release("nbr_start");
     dc->bucket_start = dc->pos_table = nullptr;
+    dc->table_build = SA_TABLE_BUILD_NONE;
+    dc->table_unsorted = 0;
     dc->num_index = 0;
     for (int b = 0; b < SA_BUFFER_DEPTH; b++) {
         dc->query[b].release("d_query_seq");
@@ -309,6 +311,8 @@ void sa_clear_ref(void) {  // seed_filter_interface.cu:103-113
         // first-touch page clearing inside the next GenerateSeedPosTable, 0.37 -> 0.11 s per 500 Mbp block).  That departs from the
         // reference, whose clearRef frees both tables: option clear_ref_frees = 1 restores it; ShutdownProcessor frees them either way.
         dc->bucket_start = dc->pos_table = nullptr;
+        dc->table_build = SA_TABLE_BUILD_NONE;
+        dc->table_unsorted = 0;
         dc->num_index = 0;
         if (opt_value("clear_ref_frees")) {
             dc->keep_bucket.release("d_index_table");
@@ -378,6 +382,8 @@ void sa_generate_seed_pos_table(const char* ref_str, size_t start_addr, uint32_t
         dc->bucket_start = dc->keep_bucket.p;
         uint32_t num_index = 0;
         bool built = false;
+        int how = SA_TABLE_BUILD_ATOMIC;  // (sa_get_table_build_info)
+        uint32_t unsorted = 0;
         // Scratch of the build.  A 500 Mbp block needs ~10 GB of it (keys, four pair arrays); from hipMalloc every block paid
         // first-touch page clearing for it inside GenerateSeedPosTable (25-60 ms per GiB: 0.25 s of a 0.37 s build).  The table
         // arena is mapped (cleared) memory that holds nothing at this point -- the neighbourhood table it is there for is filled
@@ -429,13 +435,22 @@ void sa_generate_seed_pos_table(const char* ref_str, size_t start_addr, uint32_t
             check_launch("table partition");
             if (d_err) check_memcpy(hipMemcpyAsync(&err, d_err, sizeof(uint32_t), hipMemcpyDeviceToHost, st), "partition flag");
             check_sync(st, "table partition");
+            {   // which partitions the finish kernel left to the global sort (sa_get_table_build_info): read before the scratch goes
+                size_t nflags = 0;
+                const uint8_t* d_flags = table_partition_unsorted_flags(kmer_size, part_unsorted, fine, &nflags);
+                std::vector<uint8_t> flags(nflags);
+                check_memcpy(hipMemcpy(flags.data(), d_flags, nflags, hipMemcpyDeviceToHost), "partition flags");
+                for (uint8_t f : flags) unsorted += f;
+            }
             uncarve(pairs, "partition pairs");
             uncarve(keys, "kmer keys");
             uncarve(coarse, "coarse histogram");
             uncarve(fine, "fine partitions");
             uncarve(scan_tmp, "scan temp");
             built = err == 0;  // (a tile of the third level spanned too many coarse groups -- a tiny or wildly skewed table: atomic build)
+            how = built ? (fw ? SA_TABLE_BUILD_THREE_LEVEL : SA_TABLE_BUILD_TWO_LEVEL) : SA_TABLE_BUILD_ATOMIC_GAVE_UP;
             if (!built) {
+                unsorted = 0;
                 dc->pos_table = nullptr;
                 if (opt_value("debug")) fprintf(stderr, "seed table: the partition build gave up on this table, atomic build instead\n");
             }
@@ -464,6 +479,8 @@ void sa_generate_seed_pos_table(const char* ref_str, size_t start_addr, uint32_t
         tmp_codes.release("table codes");
         dc->num_index = num_index;
         dc->nkeys = nkeys;
+        dc->table_build = how;
+        dc->table_unsorted = unsorted;
         // the neighbourhood table belongs to the table build when the processor parameters are already known (the reference
         // calls InitializeProcessor first, src/main.cpp:298 before :621); otherwise the first table-direct call builds it
         if (g_proc_init && g_packed_filter) ensure_nbr(dc);

@@ -420,6 +420,9 @@ struct DevCtx {
     DevBuf<uint64_t> keep_nbr_start;         // hipMalloc pays first-touch page clearing, 25-60 ms per GiB, inside the next block's table build
     uint32_t num_index = 0;
     uint32_t nkeys = 0;
+    int table_build = 0;                 // SA_TABLE_BUILD_*: which build made the tables above (sa_get_table_build_info; tests)
+    uint32_t table_unsorted = 0;         // ... and how many partitions its finish kernel could not hold in LDS
+    int nbr_fill = 0;                    // SA_NBR_FILL_*: which fill made the neighbourhood table below
     // sequence upload: ASCII goes through a ring of two pinned buffers into a reused device staging buffer, so the copies
     // are real asynchronous DMA on the admin stream (a pageable hipMemcpyAsync is staged synchronously by the runtime) and
     // nothing is allocated or freed per block (the reference mallocs + frees a temp per call, seed_filter_interface.cu:90-99,

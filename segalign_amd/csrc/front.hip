@@ -98,6 +98,7 @@ void nbr_release(DevCtx* dc) {
     dc->nbr_alias = false;
     dc->nbr_total = 0;
     dc->nbr_state = 0;
+    dc->nbr_fill = SA_NBR_FILL_NONE;
 }
 
 // Builds (once per table and transition mask) the neighbourhood table of the device; false when it is not available:
@@ -168,8 +169,9 @@ bool ensure_nbr(DevCtx* dc) {
             if (dbg) fprintf(stderr, "neighbourhood table: %.1f M entries, waited %.1f ms for %.1f GB of arena\n", total / 1e6, now() - t_a, need / 1e9);
             const double t_b = now();
             dc->nbr_left_skip = g_ctx_skip_seed ? g_seed_size : 0u;
-            launch_nbr_fill_ctx(dc->bucket_start, dc->pos_table, nkeys, tmask, g_shape.weight, dc->nbr_start, dc->ref2.base, dc->ref2.stride,
+            const int copy = launch_nbr_fill_ctx(dc->bucket_start, dc->pos_table, nkeys, tmask, g_shape.weight, dc->nbr_start, dc->ref2.base, dc->ref2.stride,
                                 g_seed_size, dc->nbr_left_skip, dc->nbr_ctx, two_stage ? reinterpret_cast<CtxRec*>(arena + rec_b) : nullptr, (uint32_t)dc->num_index, st);
+            dc->nbr_fill = copy == 0 ? SA_NBR_FILL_CTX_ONE_STAGE : copy == 1 ? SA_NBR_FILL_CTX_DENSE : SA_NBR_FILL_CTX_SPARSE;
             check_launch("nbr fill ctx");
             check_sync(st, "nbr fill ctx");
             if (dbg) fprintf(stderr, "neighbourhood table: context fill (%s) took %.1f ms\n", two_stage ? "two-stage" : "one-stage", now() - t_b);
@@ -181,6 +183,7 @@ bool ensure_nbr(DevCtx* dc) {
     } else if (tmask == 0) {
         dc->nbr_pos = dc->pos_table;
         dc->nbr_alias = true;
+        dc->nbr_fill = SA_NBR_FILL_ALIAS;
     } else if ([&] {  // positions only: an arena kept from an earlier (smaller) block gives its memory back first
                    if (arena_mapped(dc->arena)) {
                        arena_trim(dc->arena, 0);
@@ -195,6 +198,7 @@ bool ensure_nbr(DevCtx* dc) {
         launch_nbr_fill(dc->bucket_start, dc->pos_table, nkeys, tmask, g_shape.weight, dc->nbr_start, dc->nbr_pos, st);
         check_launch("nbr fill");
         check_sync(st, "nbr fill");
+        dc->nbr_fill = SA_NBR_FILL_POSITIONS;
     } else {
         dc->nbr_start = nullptr;
         return false;

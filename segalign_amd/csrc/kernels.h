@@ -256,6 +256,9 @@ void launch_table_partition_build(const uint32_t* keys, uint32_t num_steps, uint
                                   uint32_t* pos_a, uint32_t* key_b, uint32_t* pos_b, uint8_t* part_unsorted /* 4096 */,
                                   uint32_t* bucket_start, uint32_t* pos_table, uint32_t* fine, void* scan_tmp, uint32_t** err_flag, hipStream_t s);
 size_t table_partition_fine_words(int weight);
+// the finish kernel's "did not fit my LDS" bytes of a finished partition build, one per partition (sa_get_table_build_info): the
+// coarse flags (two levels), or the flags inside `fine` (three levels); *count = how many
+const uint8_t* table_partition_unsorted_flags(int weight, const uint8_t* part_unsorted, const uint32_t* fine, size_t* count);
 
 // ---- seeds.hip -------------------------------------------------------------------------------------------------
 // device-side seeder: valid flags for query positions [start,end), then ordered emission

@@ -41,8 +41,8 @@ void launch_nbr_fill(const uint32_t* bucket_start, const uint32_t* pos_table, ui
                      const uint64_t* nbr_start, uint32_t* nbr_pos, hipStream_t s);
 
 // the table as context records (kernels.h CtxRec); scratch: room for num_index records (nullptr: every entry cuts its context out
-// of the target itself)
-void launch_nbr_fill_ctx(const uint32_t* bucket_start, const uint32_t* pos_table, uint32_t nkeys, uint32_t tmask, int weight,
+// of the target itself).  Returns which copy ran: 0 one stage, 1 two stages with a wave per key, 2 two stages with a lane per key
+int launch_nbr_fill_ctx(const uint32_t* bucket_start, const uint32_t* pos_table, uint32_t nkeys, uint32_t tmask, int weight,
                          const uint64_t* nbr_start, const uint8_t* ref2, size_t ref2_stride, uint32_t seed_size, uint32_t left_skip, CtxRec* ctx,
                          CtxRec* scratch, uint32_t num_index, hipStream_t s);
 

@@ -200,22 +200,24 @@ __global__ __launch_bounds__(256) void nbr_fill_ctx_kernel(const uint32_t* __res
     }
 }
 
-void launch_nbr_fill_ctx(const uint32_t* bucket_start, const uint32_t* pos_table, uint32_t nkeys, uint32_t tmask, int weight,
-                         const uint64_t* nbr_start, const uint8_t* ref2, size_t ref2_stride, uint32_t seed_size, uint32_t left_skip, CtxRec* ctx,
-                         CtxRec* scratch, uint32_t num_index, hipStream_t s) {
+int launch_nbr_fill_ctx(const uint32_t* bucket_start, const uint32_t* pos_table, uint32_t nkeys, uint32_t tmask, int weight,
+                        const uint64_t* nbr_start, const uint8_t* ref2, size_t ref2_stride, uint32_t seed_size, uint32_t left_skip, CtxRec* ctx,
+                        CtxRec* scratch, uint32_t num_index, hipStream_t s) {
     if (scratch) {
         hipLaunchKernelGGL(ctx_by_index_kernel, dim3(8192), dim3(256), 0, s, pos_table, num_index, ref2, ref2_stride, seed_size, left_skip,
                            reinterpret_cast<uint4*>(scratch));
-        if (num_index < nkeys)  // (less than one position per bucket: a lane per key)
+        if (num_index < nkeys) {  // (less than one position per bucket: a lane per key)
             hipLaunchKernelGGL(nbr_copy_ctx_sparse_kernel, dim3(8192), dim3(256), 0, s, bucket_start, nkeys, tmask, weight, nbr_start,
                                reinterpret_cast<const uint4*>(scratch), reinterpret_cast<uint4*>(ctx));
-        else
-            hipLaunchKernelGGL(nbr_copy_ctx_kernel, dim3(8192), dim3(256), 0, s, bucket_start, nkeys, tmask, weight, nbr_start,
-                               reinterpret_cast<const uint4*>(scratch), reinterpret_cast<uint4*>(ctx));
-        return;
+            return 2;
+        }
+        hipLaunchKernelGGL(nbr_copy_ctx_kernel, dim3(8192), dim3(256), 0, s, bucket_start, nkeys, tmask, weight, nbr_start,
+                           reinterpret_cast<const uint4*>(scratch), reinterpret_cast<uint4*>(ctx));
+        return 1;
     }
     hipLaunchKernelGGL(nbr_fill_ctx_kernel, dim3(8192), dim3(256), 0, s, bucket_start, pos_table, nkeys, tmask, weight, nbr_start, ref2,
                        ref2_stride, seed_size, left_skip, reinterpret_cast<uint4*>(ctx));
+    return 0;
 }
 
 void launch_nbr_count(const uint32_t* bucket_start, uint32_t nkeys, uint32_t tmask, int weight, uint32_t* cnt, uint32_t* overflow,

@@ -451,6 +451,15 @@ size_t table_partition_fine_words(int weight) {
     return 3 * n + 1 + n / 4 + 16;
 }
 size_t table_partition_part_start_words() { return (1u << TB_COARSE_BITS) + 1; }
+const uint8_t* table_partition_unsorted_flags(int weight, const uint8_t* part_unsorted, const uint32_t* fine, size_t* count) {
+    if (2 * weight <= 2 * TB_COARSE_BITS) {
+        *count = (size_t)1 << TB_COARSE_BITS;
+        return part_unsorted;
+    }
+    const size_t n = (size_t)1 << TB_FINE_BITS;
+    *count = n;
+    return reinterpret_cast<const uint8_t*>(fine + 3 * n + 1);  // hist | part_start (+1) | cursor | flags (launch_table_partition_build)
+}
 
 void launch_table_keys(const uint8_t* ref, uint32_t num_steps, uint32_t start_offset, uint32_t step, SeedShape sh, uint32_t* keys,
                        uint32_t* coarse_hist, hipStream_t s) {
@@ -494,7 +503,8 @@ void launch_table_partition_build(const uint32_t* keys, uint32_t num_steps, uint
         uint32_t* hist18 = fine;
         uint32_t* start18 = hist18 + nfine;
         uint32_t* cursor18 = start18 + nfine + 1;
-        uint8_t* unsorted18 = reinterpret_cast<uint8_t*>(cursor18 + nfine);
+        size_t nflags = 0;
+        uint8_t* unsorted18 = const_cast<uint8_t*>(table_partition_unsorted_flags(weight, nullptr, fine, &nflags));  // == cursor18 + nfine
         uint32_t* err = reinterpret_cast<uint32_t*>(unsorted18 + nfine);
         if (err_flag) *err_flag = err;
         (void)hipMemsetAsync(err, 0, sizeof(uint32_t), s);

@@ -38,6 +38,7 @@ C_ABI_SYMBOLS = [
     "sa_seed_interval", "sa_seed_and_filter_chunks", "sa_max_chunks_per_call", "sa_get_chunks_per_call", "sa_extend_hits", "sa_order_hsps",
     "sa_order_hsps_segs",
     "sa_get_lookup_mode", "sa_get_neighbourhood_entries",
+    "sa_get_table_build_info", "sa_copy_neighbourhood_starts", "sa_copy_neighbourhood_records",
     "sa_seed_calls", "sa_count_call_hits", "sa_count_chunk_hits", "sa_get_wga_chunk", "sa_release_arena", "sa_set_option", "sa_reset_option", "sa_get_option", "sa_option_count", "sa_option_name", "sa_get_audit",
     "sa_gapped_extend", "sa_free_gapped", "sa_gapped_align", "sa_free_gapped_align", "sa_gapped_align_greedy",
     "sa_chain_hsps", "sa_free_chain", "sa_chain_hsps_all", "sa_free_chain_all",
@@ -149,6 +150,14 @@ class CallStats(C.Structure):
                 ("device", C.c_int), ("lookup_path", C.c_int), ("path_flags", C.c_uint32), ("num_forwarded", C.c_uint64)]
 
 
+class TableBuildInfo(C.Structure):  # sa_table_build_info
+    _fields_ = [("build", C.c_int32), ("unsorted_partitions", C.c_uint32), ("nbr_fill", C.c_int32), ("left_skip", C.c_uint32)]
+
+
+TABLE_BUILD_NONE, TABLE_BUILD_TWO_LEVEL, TABLE_BUILD_THREE_LEVEL, TABLE_BUILD_ATOMIC, TABLE_BUILD_ATOMIC_GAVE_UP = 0, 1, 2, 3, 4
+NBR_FILL_NONE, NBR_FILL_ALIAS, NBR_FILL_POSITIONS, NBR_FILL_CTX_ONE_STAGE, NBR_FILL_CTX_DENSE, NBR_FILL_CTX_SPARSE = 0, 1, 2, 3, 4, 5
+CTX_DTYPE = np.dtype([("pos", "<u4"), ("w", "<u4", (7,))])  # CtxRec: a neighbourhood entry with its target context
+
 _lib = None
 
 
@@ -220,6 +229,12 @@ def lib():
     L.sa_extend_hits.restype = C.c_size_t
     L.sa_extend_hits.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]
     L.sa_get_neighbourhood_entries.restype = C.c_uint64
+    L.sa_get_table_build_info.restype = C.c_int
+    L.sa_get_table_build_info.argtypes = [C.POINTER(TableBuildInfo)]
+    L.sa_copy_neighbourhood_starts.restype = C.c_int
+    L.sa_copy_neighbourhood_starts.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.sa_copy_neighbourhood_records.restype = C.c_int
+    L.sa_copy_neighbourhood_records.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
     L.sa_version.restype = C.c_char_p
     L.sa_seed_calls.restype = C.c_size_t
     L.sa_seed_calls.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_void_p, C.POINTER(CallStats)]
@@ -795,6 +810,37 @@ def lookup_mode():
 
 def neighbourhood_entries():
     return int(lib().sa_get_neighbourhood_entries())
+
+
+def table_build_info():
+    """How the resident tables of device 0 were made (sa_get_table_build_info; test entry): {"build": TABLE_BUILD_*,
+    "unsorted_partitions", "nbr_fill": NBR_FILL_*, "left_skip"}."""
+    st = TableBuildInfo()
+    if lib().sa_get_table_build_info(C.byref(st)) != 0:
+        raise RuntimeError("sa_get_table_build_info before InitializeInterface")
+    return {k: int(getattr(st, k)) for k, _ in TableBuildInfo._fields_}
+
+
+def copy_neighbourhood_starts(first_key=0, count=None, dev=0):
+    """nbr_start[first_key : first_key + count] (uint64; count None: up to and including the closing word at 4^kmer_size)."""
+    if count is None:
+        count = int(lib().sa_get_index_table_size()) + 1 - int(first_key)
+    out = np.empty(max(int(count), 0), dtype=np.uint64)
+    if lib().sa_copy_neighbourhood_starts(dev, int(first_key), int(count), out.ctypes.data) != 0:
+        raise RuntimeError("sa_copy_neighbourhood_starts failed (table not built, or range outside it)")
+    return out
+
+
+def copy_neighbourhood_records(first_entry=0, count=None, dev=0):
+    """Entries [first_entry, first_entry + count) of the neighbourhood table (count None: to its end) -> (mode, array): CTX_DTYPE
+    records in lookup mode 2, uint32 seed start positions in mode 1."""
+    if count is None:
+        count = neighbourhood_entries() - int(first_entry)
+    buf = np.empty(max(int(count), 0) * 8, dtype=np.uint32)  # (room for the larger of the two)
+    mode = lib().sa_copy_neighbourhood_records(dev, int(first_entry), int(count), buf.ctypes.data)
+    if mode not in (1, 2):
+        raise RuntimeError("sa_copy_neighbourhood_records failed (table not built, or range outside it)")
+    return mode, (buf.view(CTX_DTYPE).copy() if mode == 2 else buf[:max(int(count), 0)].copy())
 
 
 def filter_mode():
