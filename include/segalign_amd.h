@@ -335,6 +335,78 @@ int sa_copy_neighbourhood_starts(int dev, uint64_t first_key, uint64_t count, ui
  * uint32 seed start positions in mode 1.  Returns which (2 or 1), or -1 with a message as above. */
 int sa_copy_neighbourhood_records(int dev, uint64_t first_entry, uint64_t count, void* dst);
 
+/* Test entry (read-only; tests/test_gpu_probe_regimes.py, DESIGN.md 4.4'): the FRONT of a table-direct call alone -- position probe,
+ * workgroup sums, compaction, head bits, chunk plans -- and everything it wrote.  [start, end) of strand `rev` of query `buffer` on
+ * the resident target is clipped to the positions whose seed window lies inside the query and cut into sa_get_wga_chunk()-sized
+ * chunks from `start` on, exactly as sa_seed_and_filter_chunks lays them (the number of chunks comes from the unclipped end: chunks
+ * behind the clip are empty); a slot is taken from the pool the way calls take one, the probe runs, nothing else does: no filter, no
+ * extension, no HSPs, and the calling thread's call statistics stay as they were.  rm != 0: the target is its own query (`buffer` is
+ * ignored, sa_rm_send_query_write_request has provided the minus strand) and the plan is made with the repeat masker's 64-bit hit
+ * arithmetic.
+ * Returns SA_PROBE_OK with *out filled, or -- with *out zeroed but for `status` and nothing to free --
+ *   SA_PROBE_NO_TABLE        before sa_initialize_processor, without a seed position table, or for a buffer id out of range;
+ *   SA_PROBE_NOT_ELIGIBLE    calls of this processor do not take the table-direct path (options no_td / count_examined, no room for the
+ *                            neighbourhood table, a query whose packed copies are missing -- rm != 0 before
+ *                            sa_rm_send_query_write_request -- or too large for the class filter);
+ *   SA_PROBE_EMPTY_RANGE     end <= start after the clip (a strand that has not been sent has length 0: every range is empty);
+ *   SA_PROBE_TOO_MANY_CHUNKS the range holds more than sa_max_chunks_per_call() chunks.
+ * The pool hands out the slot that was given back last, so two consecutive calls of one thread (with no other call in flight) land in
+ * the same slot: `slot` says which it was. */
+#define SA_PROBE_OK 0
+#define SA_PROBE_NO_TABLE 1
+#define SA_PROBE_NOT_ELIGIBLE 2
+#define SA_PROBE_EMPTY_RANGE 3
+#define SA_PROBE_TOO_MANY_CHUNKS 4
+#define SA_PROBE_MAX_ITER 8
+#define SA_PROBE_PLAN_OVERFLOW 0xFFFFFFFFu
+typedef struct sa_probe_plan {   /* the plan of one chunk */
+    uint64_t hit_base;           /* call-wide index of the chunk's first hit */
+    uint64_t num_hits;
+    uint64_t upto[SA_PROBE_MAX_ITER]; /* call-wide hit offsets where the chunk's reference iterations end (src/seed_filter.cu:718-745); entries
+                                    from n_iter on hold hit_base */
+    uint32_t num_valid;          /* valid seed positions of the chunk */
+    uint32_t m_lo, m_hi;         /* its range of records */
+    uint32_t n_iter;             /* 0: no hits; SA_PROBE_PLAN_OVERFLOW: more than SA_PROBE_MAX_ITER iterations, or (rm == 0) hit counts that
+                                    wrap the reference's uint32 arithmetic */
+} sa_probe_plan;
+typedef struct sa_probe_bound {  /* exclusive sums in front of a chunk boundary */
+    uint64_t hits;
+    uint32_t nonempty, valid;    /* positions with hits, positions with a valid seed window */
+} sa_probe_bound;
+typedef struct sa_probe_record { /* a non-empty position */
+    uint32_t prefix;             /* call-wide index of its first hit */
+    uint32_t qpos;
+    uint64_t off;                /* where its run starts in the neighbourhood table */
+} sa_probe_record;
+typedef struct sa_probe_result {
+    int32_t status;              /* SA_PROBE_* */
+    int32_t slot;                /* index of the slot the call ran in (device 0 first) */
+    uint32_t ret;                /* what the front returned: seed words of the call, 0 (no valid position), UINT32_MAX (refused) */
+    uint32_t words;              /* seed words per valid position */
+    uint32_t start, end;         /* the range after the clip */
+    uint32_t chunk;              /* the chunk size of the grid */
+    uint32_t num_chunks;         /* K */
+    uint64_t hits;               /* hits of the call */
+    uint32_t num_records;        /* non-empty positions (records[] holds one more: the sentinel) */
+    uint32_t lookup_mode;        /* 2: the context table is resident and a head-bit map was made; 1: none */
+    uint32_t regrown;            /* this call raised SA_PATH_HEAD_BITS_REGROWN */
+    uint32_t num_seg_end;        /* sum of n_iter over the planned chunks (at most 512 are written) */
+    uint64_t head_words_before;  /* head-bit words the slot owned before the call, and after it */
+    uint64_t head_words_after;
+    uint64_t num_head_words;     /* words in head_bits[]: ((hits + 63) >> 6) * 2 + 16 in mode 2, else 0 */
+    uint64_t num_td_chunk;       /* ceil(hits / 4096) */
+    sa_probe_plan* plans;        /* [num_chunks] */
+    sa_probe_bound* bounds;      /* [num_chunks + 1] */
+    sa_probe_record* records;    /* [num_records + 1] */
+    uint32_t* head_bits;         /* [num_head_words] bit g <=> a record starts at hit g */
+    uint32_t* td_chunk;          /* [num_td_chunk] the record that holds hit 4096 k */
+    uint64_t* seg_end;           /* [min(num_seg_end, 512)] the iteration ends of the call in hit order */
+    uint64_t* t_off;             /* [end - start] per position: run offset | 1 << 63 when the window is valid */
+    uint32_t* t_cnt;             /* [end - start] per position: run length */
+} sa_probe_result;
+int sa_probe_call(uint32_t start, uint32_t end, int rev, uint32_t buffer, int rm, sa_probe_result* out);
+void sa_free_probe_call(sa_probe_result* r); /* frees the arrays of *r (not r itself) and zeroes their pointers */
+
 /* Per-kernel HIP-event timing on the engine's own streams (bench.py's roofline leg). */
 void sa_profile_enable(int on);
 void sa_profile_reset(void);

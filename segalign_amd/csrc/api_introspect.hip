@@ -5,6 +5,14 @@
 
 using namespace sa;
 
+// a malloc'ed host copy of n elements of a device array, queued on the stream (sa_probe_call)
+template <typename T>
+static T* probe_download(const T* src, size_t n, hipStream_t st, const char* what) {
+    T* h = (T*)malloc(std::max<size_t>(n, 1) * sizeof(T));
+    if (n) check_memcpy(hipMemcpyAsync(h, src, n * sizeof(T), hipMemcpyDeviceToHost, st), what);
+    return h;
+}
+
 extern "C" {
 
 // ---- introspection --------------------------------------------------------------------------------------------------
@@ -106,6 +114,106 @@ int sa_copy_neighbourhood_records(int dev, uint64_t first_entry, uint64_t count,
     }
     if (count) check_memcpy(hipMemcpy(dst, dc->nbr_pos + first_entry, count * sizeof(uint32_t), hipMemcpyDeviceToHost), "neighbourhood positions");
     return 1;
+}
+
+// ---- the front of a table-direct call alone (tests/test_gpu_probe_regimes.py, DESIGN.md 4.4') -------------------------------------------
+// The range is clipped and cut into chunks as chunks_pass (api_calls.hip) does it, a slot is taken as calls take one, the unchanged
+// td_front runs, and what it left in the slot is copied out.  Nothing of a call's later stages runs; t_stats is left alone.
+static_assert(sizeof(sa_probe_plan) == sizeof(TdPlan) && offsetof(sa_probe_plan, upto) == offsetof(TdPlan, upto) &&
+                  offsetof(sa_probe_plan, num_valid) == offsetof(TdPlan, num_valid) && offsetof(sa_probe_plan, n_iter) == offsetof(TdPlan, n_iter) &&
+                  SA_PROBE_MAX_ITER == TD_MAX_ITER && SA_PROBE_PLAN_OVERFLOW == TD_PLAN_OVERFLOW,
+              "sa_probe_plan is TdPlan");
+static_assert(sizeof(sa_probe_record) == sizeof(TdRec) && offsetof(sa_probe_record, off) == offsetof(TdRec, off), "sa_probe_record is TdRec");
+static_assert(sizeof(sa_probe_bound) == 16, "sa_probe_bound is the (hits, non-empty, valid) triple of probe.hip");
+
+void sa_free_probe_call(sa_probe_result* r) {
+    if (!r) return;
+    free(r->plans); free(r->bounds); free(r->records); free(r->head_bits); free(r->td_chunk); free(r->seg_end); free(r->t_off); free(r->t_cnt);
+    r->plans = nullptr; r->bounds = nullptr; r->records = nullptr; r->head_bits = nullptr; r->td_chunk = nullptr; r->seg_end = nullptr;
+    r->t_off = nullptr; r->t_cnt = nullptr;
+}
+
+int sa_probe_call(uint32_t start, uint32_t end, int rev, uint32_t buffer, int rm, sa_probe_result* o) {
+    memset(o, 0, sizeof(*o));
+    auto leave = [&](int status) { o->status = status; return status; };
+    if (g_ndev <= 0 || !g_proc_init || (!rm && buffer >= SA_BUFFER_DEPTH)) return leave(SA_PROBE_NO_TABLE);
+    const uint32_t chunk = g_wga_chunk;
+    const uint64_t K64 = end > start && chunk ? ((uint64_t)end - start + chunk - 1) / chunk : 0;
+    if (K64 > (uint64_t)SA_MAX_CHUNKS) return leave(SA_PROBE_TOO_MANY_CHUNKS);
+    const int K = (int)K64;
+    Slot* sl = acquire_slot();
+    DevCtx* dc = sl->ctx;
+    auto give_back = [&](int status) {
+        prof_flush(sl);
+        t_front_flags = 0;
+        release_slot(sl);
+        if (status != SA_PROBE_OK) memset(o, 0, sizeof(*o));
+        return leave(status);
+    };
+    for (int d = 0, k = 0; d < g_ndev; d++)
+        for (int s = 0; s < SLOTS_PER_DEVICE; s++, k++)
+            if (&g_dev[d]->slots[s] == sl) o->slot = k;
+    if (!dc->bucket_start || !dc->pos_table) return give_back(SA_PROBE_NO_TABLE);
+    const uint8_t* q;
+    uint32_t qlen;
+    const PackedBuf *q4, *q2_own, *q2_other;
+    if (rm) {
+        q = rev ? dc->ref_rc.codes : dc->ref.codes;
+        qlen = dc->ref.len;
+        q4 = rev ? &dc->ref4_rc : &dc->ref4;
+        q2_own = rev ? &dc->refq2_rc : &dc->refq2;
+        q2_other = rev ? &dc->refq2 : &dc->refq2_rc;
+    } else {
+        q = rev ? dc->query_rc[buffer].codes : dc->query[buffer].codes;
+        qlen = g_query_len[buffer];
+        q4 = rev ? &dc->query4_rc[buffer] : &dc->query4[buffer];
+        q2_own = rev ? &dc->query2_rc[buffer] : &dc->query2[buffer];
+        q2_other = rev ? &dc->query2[buffer] : &dc->query2_rc[buffer];
+    }
+    if (!q) qlen = 0;
+    const uint32_t lim = qlen >= g_seed_size ? qlen - g_seed_size + 1 : 0;
+    const uint32_t send = std::min(end, lim);  // a seed window must lie inside the block
+    if (K == 0 || send <= start) return give_back(SA_PROBE_EMPTY_RANGE);
+    if (!td_eligible(dc, q4, q2_own, q2_other)) return give_back(SA_PROBE_NOT_ELIGIBLE);
+    uint32_t bpos[SA_MAX_CHUNKS + 1];
+    for (int c = 0; c <= K; c++) bpos[c] = (uint32_t)std::min<uint64_t>((uint64_t)start + (uint64_t)c * chunk, send);
+    o->head_words_before = sl->td_bits.cap;
+    t_front_flags = 0;
+    uint32_t words = 0;
+    o->ret = td_front(dc, sl, q, K, bpos, rm ? 1 : 0, &words);  // (synchronises the slot's stream)
+    o->regrown = (t_front_flags & SA_PATH_HEAD_BITS_REGROWN) ? 1u : 0u;
+    o->words = words;
+    o->start = start;
+    o->end = send;
+    o->chunk = K > 1 ? chunk : send - start;
+    o->num_chunks = (uint32_t)K;
+    o->lookup_mode = dc->nbr_ctx ? 2u : 1u;
+    o->head_words_after = sl->td_bits.cap;
+    hipStream_t st = sl->stream;
+    const uint32_t n = send - start;
+    o->plans = (sa_probe_plan*)malloc((size_t)K * sizeof(sa_probe_plan));
+    memcpy(o->plans, sl->h_td_plan, (size_t)K * sizeof(TdPlan));
+    o->bounds = probe_download(reinterpret_cast<const sa_probe_bound*>(sl->d_td_bounds), (size_t)K + 1, st, "probe bounds");
+    check_sync(st, "probe bounds");
+    o->hits = o->bounds[K].hits;
+    o->num_records = o->bounds[K].nonempty;
+    uint64_t n_iter = 0;
+    for (int c = 0; c < K; c++)
+        if (o->plans[c].n_iter != TD_PLAN_OVERFLOW) n_iter += o->plans[c].n_iter;
+    o->num_seg_end = (uint32_t)n_iter;
+    // (what lies beyond these counts was not written by this call; every count is clamped to what the slot owns)
+    const uint64_t need_words = ((o->hits + 63) >> 6) * 2 + 16;
+    o->num_head_words = dc->nbr_ctx ? std::min<uint64_t>(need_words, sl->td_bits.cap) : 0;
+    o->num_td_chunk = std::min<uint64_t>((o->hits + TD_CHUNK_HITS - 1) / TD_CHUNK_HITS, TD_CHUNK_CAP);
+    o->records = probe_download(reinterpret_cast<const sa_probe_record*>(sl->td_rec.p), std::min<size_t>((size_t)o->num_records + 1, sl->td_rec.cap), st,
+                                "probe records");
+    o->head_bits = probe_download(sl->td_bits.p, (size_t)o->num_head_words, st, "probe head bits");
+    o->td_chunk = probe_download(sl->td_chunk.p, (size_t)o->num_td_chunk, st, "probe chunk starts");
+    o->seg_end = probe_download(sl->d_seg_end, (size_t)std::min<uint64_t>(n_iter, MAX_SEGS), st, "probe segment ends");
+    o->t_off = probe_download(sl->td_toff.p, (size_t)n, st, "probe scratch");
+    o->t_cnt = probe_download(sl->td_tcnt.p, (size_t)n, st, "probe scratch");
+    check_sync(st, "probe copies");
+    return give_back(SA_PROBE_OK);
 }
 
 // The ordering stage alone (dedup.hip) on records the host hands in, as ONE dedup scope: what the reference does to the anchors of an

@@ -39,6 +39,7 @@ C_ABI_SYMBOLS = [
     "sa_order_hsps_segs",
     "sa_get_lookup_mode", "sa_get_neighbourhood_entries",
     "sa_get_table_build_info", "sa_copy_neighbourhood_starts", "sa_copy_neighbourhood_records",
+    "sa_probe_call", "sa_free_probe_call",
     "sa_seed_calls", "sa_count_call_hits", "sa_count_chunk_hits", "sa_get_wga_chunk", "sa_release_arena", "sa_set_option", "sa_reset_option", "sa_get_option", "sa_option_count", "sa_option_name", "sa_get_audit",
     "sa_gapped_extend", "sa_free_gapped", "sa_gapped_align", "sa_free_gapped_align", "sa_gapped_align_greedy",
     "sa_chain_hsps", "sa_free_chain", "sa_chain_hsps_all", "sa_free_chain_all",
@@ -154,6 +155,23 @@ class TableBuildInfo(C.Structure):  # sa_table_build_info
     _fields_ = [("build", C.c_int32), ("unsorted_partitions", C.c_uint32), ("nbr_fill", C.c_int32), ("left_skip", C.c_uint32)]
 
 
+# sa_probe_call (test entry, DESIGN.md 4.4'): the front of a table-direct call and what it wrote
+PROBE_OK, PROBE_NO_TABLE, PROBE_NOT_ELIGIBLE, PROBE_EMPTY_RANGE, PROBE_TOO_MANY_CHUNKS = 0, 1, 2, 3, 4
+PROBE_MAX_ITER, PROBE_PLAN_OVERFLOW, PROBE_VALID = 8, 0xFFFFFFFF, 1 << 63
+PROBE_PLAN_DTYPE = np.dtype([("hit_base", "<u8"), ("num_hits", "<u8"), ("upto", "<u8", (PROBE_MAX_ITER,)), ("num_valid", "<u4"), ("m_lo", "<u4"),
+                             ("m_hi", "<u4"), ("n_iter", "<u4")])  # sa_probe_plan
+PROBE_BOUND_DTYPE = np.dtype([("hits", "<u8"), ("nonempty", "<u4"), ("valid", "<u4")])  # sa_probe_bound
+PROBE_REC_DTYPE = np.dtype([("prefix", "<u4"), ("qpos", "<u4"), ("off", "<u8")])  # sa_probe_record
+
+
+class ProbeResult(C.Structure):  # sa_probe_result
+    _fields_ = [("status", C.c_int32), ("slot", C.c_int32), ("ret", C.c_uint32), ("words", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32),
+                ("chunk", C.c_uint32), ("num_chunks", C.c_uint32), ("hits", C.c_uint64), ("num_records", C.c_uint32), ("lookup_mode", C.c_uint32),
+                ("regrown", C.c_uint32), ("num_seg_end", C.c_uint32), ("head_words_before", C.c_uint64), ("head_words_after", C.c_uint64),
+                ("num_head_words", C.c_uint64), ("num_td_chunk", C.c_uint64), ("plans", C.c_void_p), ("bounds", C.c_void_p), ("records", C.c_void_p),
+                ("head_bits", C.c_void_p), ("td_chunk", C.c_void_p), ("seg_end", C.c_void_p), ("t_off", C.c_void_p), ("t_cnt", C.c_void_p)]
+
+
 TABLE_BUILD_NONE, TABLE_BUILD_TWO_LEVEL, TABLE_BUILD_THREE_LEVEL, TABLE_BUILD_ATOMIC, TABLE_BUILD_ATOMIC_GAVE_UP = 0, 1, 2, 3, 4
 NBR_FILL_NONE, NBR_FILL_ALIAS, NBR_FILL_POSITIONS, NBR_FILL_CTX_ONE_STAGE, NBR_FILL_CTX_DENSE, NBR_FILL_CTX_SPARSE = 0, 1, 2, 3, 4, 5
 CTX_DTYPE = np.dtype([("pos", "<u4"), ("w", "<u4", (7,))])  # CtxRec: a neighbourhood entry with its target context
@@ -235,6 +253,9 @@ def lib():
     L.sa_copy_neighbourhood_starts.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
     L.sa_copy_neighbourhood_records.restype = C.c_int
     L.sa_copy_neighbourhood_records.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.sa_probe_call.restype = C.c_int
+    L.sa_probe_call.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.POINTER(ProbeResult)]
+    L.sa_free_probe_call.argtypes = [C.POINTER(ProbeResult)]
     L.sa_version.restype = C.c_char_p
     L.sa_seed_calls.restype = C.c_size_t
     L.sa_seed_calls.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_void_p, C.POINTER(CallStats)]
@@ -841,6 +862,33 @@ def copy_neighbourhood_records(first_entry=0, count=None, dev=0):
     if mode not in (1, 2):
         raise RuntimeError("sa_copy_neighbourhood_records failed (table not built, or range outside it)")
     return mode, (buf.view(CTX_DTYPE).copy() if mode == 2 else buf[:max(int(count), 0)].copy())
+
+
+def ProbeCall(start, end, rev=False, buffer=0, rm=False):
+    """The front of a table-direct call alone (sa_probe_call; test entry): [start, end) of a strand of the resident query (rm: of the
+    target itself) is clipped and cut into wga_chunk-sized chunks as SeedAndFilterChunks does it, probed, compacted and planned.
+    -> dict with "status" (PROBE_*); with PROBE_OK also the scalars of sa_probe_result and the arrays "plans" (PROBE_PLAN_DTYPE),
+    "bounds" (PROBE_BOUND_DTYPE), "records" (PROBE_REC_DTYPE, sentinel included), "head_bits" (uint32), "td_chunk" (uint32), "seg_end"
+    (uint64), "t_off" (uint64, PROBE_VALID set for a valid window), "t_cnt" (uint32)."""
+    r = ProbeResult()
+    status = lib().sa_probe_call(int(start), int(end), int(bool(rev)), int(buffer), int(bool(rm)), C.byref(r))
+    if status != PROBE_OK:
+        return {"status": int(status)}
+    try:
+        def take(ptr, count, dtype):
+            dtype = np.dtype(dtype)
+            if not count:
+                return np.zeros(0, dtype=dtype)
+            return np.frombuffer((C.c_char * (int(count) * dtype.itemsize)).from_address(ptr), dtype=dtype).copy()
+        out = {k: int(getattr(r, k)) for k, t in ProbeResult._fields_ if t is not C.c_void_p}
+        n = out["end"] - out["start"]
+        out.update(plans=take(r.plans, r.num_chunks, PROBE_PLAN_DTYPE), bounds=take(r.bounds, r.num_chunks + 1, PROBE_BOUND_DTYPE),
+                   records=take(r.records, r.num_records + 1, PROBE_REC_DTYPE), head_bits=take(r.head_bits, r.num_head_words, np.uint32),
+                   td_chunk=take(r.td_chunk, r.num_td_chunk, np.uint32), seg_end=take(r.seg_end, min(r.num_seg_end, 512), np.uint64),
+                   t_off=take(r.t_off, n, np.uint64), t_cnt=take(r.t_cnt, n, np.uint32))
+        return out
+    finally:
+        lib().sa_free_probe_call(C.byref(r))
 
 
 def filter_mode():

@@ -32,6 +32,25 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in L.sa_version()
 
 
+def test_probe_entry_structs_have_the_headers_layout():
+    """sa_probe_call hands arrays of sa_probe_plan / sa_probe_bound / sa_probe_record and one sa_probe_result to the host: the ctypes and
+    numpy restatements in engine.py have the sizes the header's fields add up to (the library asserts the same against its own structs)"""
+    import ctypes as C
+    from segalign_amd import engine as E
+    assert E.PROBE_PLAN_DTYPE.itemsize == 8 + 8 + 8 * E.PROBE_MAX_ITER + 4 * 4 == 96
+    assert E.PROBE_BOUND_DTYPE.itemsize == 16 and E.PROBE_REC_DTYPE.itemsize == 16
+    assert C.sizeof(E.ProbeResult) == 8 * 4 + 8 + 4 * 4 + 4 * 8 + 8 * C.sizeof(C.c_void_p)
+    hdr = open(os.path.join(ROOT, "include", "segalign_amd.h")).read()
+    body = hdr[hdr.index("typedef struct sa_probe_result {"):hdr.index("} sa_probe_result;")]
+    decls = re.findall(r"^\s+(?:u?int\d+_t|sa_probe_\w+\*|uint\d+_t\*)\s+([\w, ]+);", body, flags=re.M)
+    fields = [n.strip() for d in decls for n in d.split(",")]
+    assert fields == [n for n, _ in E.ProbeResult._fields_], fields
+    for name, value in (("SA_PROBE_OK", E.PROBE_OK), ("SA_PROBE_NO_TABLE", E.PROBE_NO_TABLE), ("SA_PROBE_NOT_ELIGIBLE", E.PROBE_NOT_ELIGIBLE),
+                        ("SA_PROBE_EMPTY_RANGE", E.PROBE_EMPTY_RANGE), ("SA_PROBE_TOO_MANY_CHUNKS", E.PROBE_TOO_MANY_CHUNKS),
+                        ("SA_PROBE_MAX_ITER", E.PROBE_MAX_ITER)):
+        assert re.search(r"#define %s %d\b" % (name, value), hdr), name
+
+
 def test_product_never_touches_the_oracle():
     """The product path must not import, link or execute anything under oracle/ (no CPU fallback)."""
     pkg = os.path.join(ROOT, "segalign_amd")
