@@ -1023,6 +1023,93 @@ size_t sa_net_chains(const uint32_t* first, const uint32_t* block_start, const u
                      const uint32_t* group, size_t n_chains, const sa_net_params* p, sa_net_fill** fills, sa_net_stats* stats);
 void sa_free_net(sa_net_fill* fills);
 
+/* ---- cutting the fills of a net into sub-chains (additive; restated by tests/net_subset_model.py) ----------
+ *
+ * sa_net_subset turns every fill of a net into the part of its chain that the net gave it, as a chain of its own: clipped, rescored,
+ * ready for sa_stitch_chains and ready to be netted on the other axis.  It is the project's own contract in the spirit of UCSC's
+ * netChainSubset (not claimed to equal it).
+ *   Input: n_hsps HSPs (len = bases - 1) on strand `rev` of query buffer `buffer`; chains in CSR form, members[] / first[n_chains + 1],
+ *     exactly as sa_stitch_chains takes them (at most 1 << 22 chains, empty ones included, and 1 << 22 members, the limits that entry
+ *     checks); fills[n_fills]: the output of one sa_net_chains call whose
+ *     blocks were one block per member in member order on `axis` (0: target, block = [ref_start, ref_start + len + 1); 1: query, block =
+ *     [query_start, query_start + len + 1)), so that first_block is a position in members[].  At most 2^31 - 1 fills and 1 << 26 output
+ *     members (the sum of n_blocks).  The entry needs a resident target block and query buffer, like sa_stitch_chains.
+ *     p: only diag_pen and anti_pen are read (max_gap and min_score are not); NULL means 0, 0.  g: a gap-cost table with the
+ *     semantics and validation of sa_chain_hsps_costs, or NULL for none.  flags: SA_SUBSET_SPLIT or 0.
+ *   Validation (on the host; a message and exit code 1, like the other entries): the CSR rules of sa_stitch_chains (first[0] = 0,
+ *     first[] non-decreasing, every member names an HSP that lies inside the block, consecutive members m, m' of a chain satisfy
+ *     re_m <= rs_m' and qe_m <= qs_m'); for every fill start < end, chain < n_chains, n_blocks >= 1, first[chain] <= first_block and
+ *     first_block + n_blocks <= first[chain + 1], its first block ends after start and its last block starts before end on `axis`,
+ *     parent is -1 or an earlier index; a fill with a parent lies inside a gap of it: there are two consecutive clipped blocks k, k + 1
+ *     of the parent with end_k <= start and end <= start_k+1; diag_pen and anti_pen in 0 .. 1 << 20; the gap-cost table's rules; axis in
+ *     0 .. 1; flags <= 1; the limits above.
+ *   Clipped member: block k of a fill is the HSP members[first_block + k] cut to [start, end) on `axis`; the other coordinate moves by
+ *     the same amount, an HSP being ungapped.  The blocks of a chain ascend, so only the first and the last block of a fill can be cut,
+ *     and a single block on both sides.
+ *   Member score (int64): an uncut member keeps its score field, the value the chaining DP used.  A cut member scores the sum over its
+ *     kept columns k of sub_mat[T[rs + k] * 8 + Q[qs + k]], recomputed from the codes (a separator scores as the matrix has it, as in
+ *     sa_stitch_chains).  The score field of the output HSP is that value clamped to int32; the chain score uses the exact value.
+ *   Runs: without SA_SUBSET_SPLIT a fill is one run.  With it the fill is cut after its clipped block k whenever a fill whose parent is
+ *     this fill lies in the gap between its blocks k and k + 1.
+ *   Sub-chain: one sa_subset_chain per run, ordered by fill index, then by run.  score = the sum of its member scores minus the sum over
+ *     consecutive members m, m' of the run of pen'(m, m'): sa_chain_hsps's linear term under diag_pen / anti_pen plus, with g, the gap
+ *     cost of sa_chain_hsps_costs.  A cut changes neither re, qe of a member that has a successor in its run nor rs, qs of one that has
+ *     a predecessor, so these penalties are the ones the original links paid.
+ *   Output: out_hsps[*n_out]: the clipped members laid out run after run (fill after fill, block after block), so that a run's members
+ *     are the range first_member .. first_member + n_members - 1; the sa_subset_chain records; group is the fill's.
+ *   Consequences:
+ *     (a) With SA_SUBSET_SPLIT the hulls on `axis` of all sub-chains of a group are pairwise disjoint, at any min_space / min_fill of the
+ *         net: only fills whose parent is F lie in F's gaps, every such gap cuts F, and a gap without a child holds no fill.
+ *     (b) sa_stitch_chains on the output, with members = 0 .. *n_out - 1 and first = the runs' first_member and *n_out at the end,
+ *         passes that entry's validation; its records inherit (a), which gives single coverage of the axis.
+ *     (c) A fill that holds its whole chain in one run scores exactly the chain's score under the same p / g, provided the chain is not
+ *         joined and the score fields of its HSPs are what the DP used: f(head) is the sum of the scores minus the sum of the
+ *         penalties along the pred walk.
+ *     (d) At min_space = min_fill = 1 and on the axis the net ran on, the kept bases of all output members of a group partition the
+ *         union of the group's blocks (the consequence stated for sa_net_chains).
+ * The device marks the cuts (one thread per fill with a parent, a binary search over the parent's blocks), takes the member offsets
+ * and run heads from prefix sums, emits one clipped member per thread, rescores the cut members one wavefront each and sums
+ * score - penalty per run through a prefix sum in two's complement.  Slots and thread safety are sa_stitch_chains's. */
+#define SA_SUBSET_SPLIT 1u /* cut a fill where a child lies in one of its gaps */
+
+typedef struct sa_subset_chain { /* 56 bytes */
+    uint32_t fill;                    /* index of the fill */
+    uint32_t chain;                   /* the fill's chain: index into the input CSR */
+    uint32_t group;                   /* the fill's group */
+    uint32_t run;                     /* 0, 1, ... within the fill */
+    uint32_t first_member, n_members; /* positions in out_hsps */
+    uint32_t ref_start, ref_end;      /* the first member's start, the last member's end */
+    uint32_t query_start, query_end;
+    int64_t score;
+    uint32_t clipped;                 /* bit 0: the first member is cut, bit 1: the last member is cut */
+    uint32_t pad;
+} sa_subset_chain;
+
+typedef struct sa_subset_stats {
+    uint64_t fills;
+    uint64_t runs;            /* sub-chains returned */
+    uint64_t members;         /* output HSPs */
+    uint64_t cut_members;     /* output HSPs that are shorter than their input HSP */
+    uint64_t bases_rescored;  /* kept columns of the cut members */
+    uint64_t splits;          /* runs - fills */
+    double subset_ms;         /* device time of all kernels */
+} sa_subset_stats;
+#ifdef __cplusplus
+static_assert(sizeof(sa_subset_chain) == 56, "sa_subset_chain is 56 bytes");
+static_assert(sizeof(sa_subset_stats) == 56, "sa_subset_stats is 56 bytes");
+#else
+_Static_assert(sizeof(sa_subset_chain) == 56, "sa_subset_chain is 56 bytes");
+_Static_assert(sizeof(sa_subset_stats) == 56, "sa_subset_stats is 56 bytes");
+#endif
+
+/* Returns the number of sub-chains.  *out_hsps (*n_out entries) and *chains are malloc-ed and released with sa_free_net_subset; each is
+ * NULL when it would be empty.  axis: 0 target, 1 query.  p, g, stats: nullable. */
+size_t sa_net_subset(const sa_segment_pair* hsps, size_t n_hsps, const uint32_t* members, const uint32_t* first, size_t n_chains,
+                     const sa_net_fill* fills, size_t n_fills, int axis, int rev, uint32_t buffer, const sa_chain_params* p,
+                     const sa_chain_gap_costs* g, uint32_t flags, sa_segment_pair** out_hsps, size_t* n_out, sa_subset_chain** chains,
+                     sa_subset_stats* stats);
+void sa_free_net_subset(sa_segment_pair* out_hsps, sa_subset_chain* chains);
+
 const char* sa_version(void);
 
 #ifdef __cplusplus

@@ -37,51 +37,6 @@ struct ChainDp {
     size_t temp_bytes = 0;
 };
 
-// A gap-cost table as the kernels of hspcost.hip read it (layout: hspcost.h), or none: the linear kernels of hspchain.hip.
-struct CostImage {
-    bool on = false;
-    uint32_t w[HSPCOST_WORDS];
-};
-
-void bad_costs(const char* what, unsigned k, long long v) {
-    fprintf(stderr, "Error: ChainHsps: gap costs: %s[%u] = %lld out of range\n", what, k, v);
-    exit(1);
-}
-
-// Checks a table (contract: include/segalign_amd.h), derives the slopes and folds the three cost arrays into the image.
-void checked_costs(const sa_chain_gap_costs* g, CostImage& im) {
-    im.on = g != nullptr;
-    if (!g) return;
-    const uint32_t n = g->n;
-    if (n < 1 || n > SA_CHAIN_GAP_POINTS) bad("gap costs: n", n);
-    for (uint32_t k = 0; k < n; k++)
-        if (k == 0 ? g->pos[0] < 1 : g->pos[k] <= g->pos[k - 1]) bad_costs("pos", k, g->pos[k]);
-    const int64_t* cost[3] = {g->q_gap, g->t_gap, g->both_gap};
-    const char* name[3] = {"q_gap", "t_gap", "both_gap"};
-    const char* slope_name[3] = {"slope of q_gap", "slope of t_gap", "slope of both_gap"};
-    for (uint32_t k = 0; k < HSPCOST_POINTS; k++) im.w[k] = g->pos[std::min(k, n - 1)];
-    for (int a = 0; a < 3; a++) {
-        const int64_t* c = cost[a];
-        uint32_t slope[SA_CHAIN_GAP_POINTS];
-        for (uint32_t k = 0; k < n; k++)
-            if (c[k] < 0 || c[k] > ((int64_t)1 << 40) || (k > 0 && c[k] < c[k - 1])) bad_costs(name[a], k, c[k]);
-        for (uint32_t k = 0; k + 1 < n; k++) {
-            const int64_t sl = ((c[k + 1] - c[k]) << 16) / (int64_t)(g->pos[k + 1] - g->pos[k]);  // operands >= 0: the quotient is the floor
-            if (sl >= (int64_t)HSPCOST_SLOPE_LIMIT) bad_costs(slope_name[a], k, sl);
-            slope[k] = (uint32_t)sl;
-        }
-        slope[n - 1] = n > 1 ? slope[n - 2] : 0;
-        for (uint32_t k = 0; k < HSPCOST_POINTS; k++) {
-            const uint32_t r = std::min(k, n - 1);
-            uint32_t* row = im.w + HSPCOST_ROW0 + 4 * ((uint32_t)a * HSPCOST_POINTS + k);
-            row[0] = (uint32_t)c[r];
-            row[1] = (uint32_t)((uint64_t)c[r] >> 32);
-            row[2] = slope[r];
-            row[3] = g->pos[r];
-        }
-    }
-}
-
 // The slot's buffers, the upload, rank and the DP (spans 0 and 1 of ev) for n > 0 HSPs on the slot d.sl.  Returns with the stream
 // synchronised, G known and st's pair_evals and tile_steps counted.
 void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, uint32_t T, const CostImage& costs, ChainDp& d, ChainTimer& ev,
@@ -196,7 +151,7 @@ size_t chain_hsps(const sa_segment_pair* hsps, size_t n, const uint32_t* group, 
     ChainDp d;
     const uint32_t T = checked(p, n, d.P);
     CostImage costs;
-    checked_costs(g, costs);
+    checked_costs("ChainHsps", g, costs);
     if (n == 0) return 0;
     Slot* sl = d.sl = acquire_slot_early();
     hipStream_t s = sl->stream;
@@ -256,7 +211,7 @@ size_t chain_hsps_all(const sa_segment_pair* hsps, size_t n, const uint32_t* gro
     ChainDp d;
     const uint32_t T = checked(p, n, d.P);
     CostImage costs;
-    checked_costs(g, costs);
+    checked_costs("ChainHsps", g, costs);
     if (n == 0) return 0;
     Slot* sl = d.sl = acquire_slot_early();
     hipStream_t s = sl->stream;

@@ -15,7 +15,8 @@
 //   api_hspchain.hip   sa_chain_hsps: the best collinear chain of every group of HSPs (hspchain.hip); sa_chain_hsps_all: all chains (hsppeel.hip)
 //   api_stitch.hip     sa_stitch_chains: every chain of HSPs as one gapped alignment through its members (stitch.hip, gapped.hip's walk)
 //   api_net.hip        sa_net_chains: the chains of every group netted into fills and gaps on one axis (net.hip)
-//   post_host.h        what those four share on the host: event timing, checked launches, buffer carving, caller-owned arrays, trace batches
+//   api_netsubset.hip  sa_net_subset: the fills of a net cut into clipped, rescored sub-chains (netsubset.hip)
+//   post_host.h        what those five share on the host: event timing, checked launches, buffer carving, caller-owned arrays, trace batches
 //   gapped.hip         kernels of the gapped entries: y-drop extension of a side, trace sweep, path walk (gapped.h)
 //   cover.hip          kernels and rocPRIM steps of the greedy cover index; its sort and scan wrappers also serve api_hspchain.hip (gapped.h)
 //   hspchain.hip       kernels of the chaining DP: rank keys, gather, tile cross / resolve, group ends, members, nodes (hspchain.h)
@@ -23,6 +24,7 @@
 //   hsppeel.hip        kernels of the peel into all chains: subtree minimum, chain order, members, records (hsppeel.h)
 //   stitch.hip         kernels of the stitch: member scores, the global sweep of a link in five instances (stitch.h)
 //   net.hip            kernels of the net: priority order, hulls, and a round's search, count and emit, one wavefront per space (net.h)
+//   netsubset.hip      kernels of the net subset: cut marks, clipped members, the cut members' scores, run sums and records (netsubset.h)
 //   api_introspect.hip statistics, lookup mode, copies of device state for the tests
 #pragma once
 #include <hip/hip_runtime.h>
@@ -357,6 +359,7 @@ struct Slot {
     // sa_net_chains (api_net.hip, net.hip): the input and what the prepare step makes of it; a round's hits, counts and offsets, then the
     // final order's keys; all fills in emission order (grown with their contents kept); this round's spaces and the next one's
     DevBuf<uint8_t> net_work, net_round, net_fills, net_space[2];
+    DevBuf<uint8_t> netsubset;        // sa_net_subset (api_netsubset.hip, netsubset.hip): the fills, the members' HSPs and everything made of them
     bool early = false;               // taken from the pool that serves sa_chain_hsps before InitializeProcessor (pool.hip)
 };
 

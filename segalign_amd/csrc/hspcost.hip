@@ -26,26 +26,6 @@ struct Me {  // the node a thread owns
     uint32_t gr;
 };
 
-// The gap cost of a link with gaps dt, dq from the LDS image.  For a pair that is no link (a negative gap) the value is arbitrary but
-// every step stays in range: the search clamps x into 32 bits, the distance past the break point is clamped at 0.
-__device__ __forceinline__ int64_t gapcost(const uint32_t* img, int64_t dt, int64_t dq) {
-    const int64_t x = dt + dq;
-    const uint32_t off = dt == 0 ? 0u : dq == 0 ? HSPCOST_POINTS : 2 * HSPCOST_POINTS;
-    const uint32_t xc = ((uint64_t)x >> 32) ? 0xFFFFFFFFu : (uint32_t)x;  // pos < 2^32: the search gives the same row as with x
-    uint32_t k = 0;  // the largest k with pos[k] <= x, or 0
-    k += img[k + 8] <= xc ? 8u : 0u;
-    k += img[k + 4] <= xc ? 4u : 0u;
-    k += img[k + 2] <= xc ? 2u : 0u;
-    k += img[k + 1] <= xc ? 1u : 0u;
-    const uint4 row = ((const uint4*)(img + HSPCOST_ROW0))[off + k];  // cost low, cost high, slope, pos
-    int64_t d = x - (int64_t)row.w;
-    if (d < 0) d = 0;  // x below pos[0]: the cost of pos[0]
-    // d < 2^34 and slope < 2^27: the product from two 32-bit multiplies, below 2^61
-    const uint64_t prod = (uint64_t)(uint32_t)d * row.z + ((uint64_t)((uint32_t)((uint64_t)d >> 32) * row.z) << 32);
-    const int64_t g = (int64_t)((uint64_t)row.x | (uint64_t)row.y << 32) + (int64_t)(prod >> 16);
-    return x == 0 ? 0 : g;
-}
-
 // Offers node j (end coordinates re, qe, diagonal dg, final f fj, group gj, rank `rank`) to the node `m`.
 __device__ __forceinline__ void consider(const Me& m, int64_t re, int64_t qe, int64_t dg, int64_t fj, uint32_t gj, uint32_t rank, const Pen& P,
                                          const uint32_t* img, int64_t& best, uint32_t& bj) {
@@ -53,7 +33,7 @@ __device__ __forceinline__ void consider(const Me& m, int64_t re, int64_t qe, in
     bool ok = gj == m.gr && gap_r >= 0 && gap_q >= 0;
     if (P.max_gap) ok = ok && gap_r <= P.max_gap && gap_q <= P.max_gap;
     const int64_t dd = m.dg - dg;
-    const int64_t v = fj - (P.diag_pen * (dd < 0 ? -dd : dd) + P.anti_pen * (gap_r + gap_q) + gapcost(img, gap_r, gap_q));
+    const int64_t v = fj - (P.diag_pen * (dd < 0 ? -dd : dd) + P.anti_pen * (gap_r + gap_q) + hspcost_gapcost(img, gap_r, gap_q));
     if (ok && v > best) {
         best = v;
         bj = rank;

@@ -1,9 +1,11 @@
-// post_host.h -- the host helpers that the post-processing entries share (api_gapped.hip, api_hspchain.hip, api_stitch.hip, api_net.hip):
-// device time between events, profiled and checked launches, carving a slot buffer, malloc-ed arrays for the caller, the resident block
-// as kernel arguments, and the trace batches' packing and runs.  Host code only, everything inline or a template.
+// post_host.h -- the host helpers that the post-processing entries share (api_gapped.hip, api_hspchain.hip, api_stitch.hip, api_net.hip,
+// api_netsubset.hip): device time between events, profiled and checked launches, carving a slot buffer, malloc-ed arrays for
+// the caller, the resident block as kernel arguments, the checked gap-cost table as its device image, and the trace batches' packing and
+// runs.  Host code only, everything inline or a template.
 #pragma once
 #include "engine_internal.h"
 #include "gapped.h"
+#include "hspcost.h"
 
 namespace sa {
 
@@ -98,6 +100,55 @@ void resident_block(const char* who, const Slot* sl, int rev, uint32_t buffer, A
     a.query = q.codes;
     a.query_len = q.len;
     a.sub_mat = dc->d_sub_mat;
+}
+
+// A gap-cost table as the kernels of hspcost.hip and netsubset.hip read it (layout: hspcost.h), or none.
+struct CostImage {
+    bool on = false;
+    uint32_t w[HSPCOST_WORDS];
+};
+
+inline void bad_costs(const char* who, const char* what, unsigned k, long long v) {
+    fprintf(stderr, "Error: %s: gap costs: %s[%u] = %lld out of range\n", who, what, k, v);
+    exit(1);
+}
+
+// Checks a table (contract: include/segalign_amd.h, sa_chain_hsps_costs), derives the slopes and folds the three cost arrays into the
+// image; who's error for a table that breaks the rules.
+inline void checked_costs(const char* who, const sa_chain_gap_costs* g, CostImage& im) {
+    im.on = g != nullptr;
+    if (!g) return;
+    const uint32_t n = g->n;
+    if (n < 1 || n > SA_CHAIN_GAP_POINTS) {
+        fprintf(stderr, "Error: %s: gap costs: n = %lld out of range\n", who, (long long)n);
+        exit(1);
+    }
+    for (uint32_t k = 0; k < n; k++)
+        if (k == 0 ? g->pos[0] < 1 : g->pos[k] <= g->pos[k - 1]) bad_costs(who, "pos", k, g->pos[k]);
+    const int64_t* cost[3] = {g->q_gap, g->t_gap, g->both_gap};
+    const char* name[3] = {"q_gap", "t_gap", "both_gap"};
+    const char* slope_name[3] = {"slope of q_gap", "slope of t_gap", "slope of both_gap"};
+    for (uint32_t k = 0; k < HSPCOST_POINTS; k++) im.w[k] = g->pos[std::min(k, n - 1)];
+    for (int a = 0; a < 3; a++) {
+        const int64_t* c = cost[a];
+        uint32_t slope[SA_CHAIN_GAP_POINTS];
+        for (uint32_t k = 0; k < n; k++)
+            if (c[k] < 0 || c[k] > ((int64_t)1 << 40) || (k > 0 && c[k] < c[k - 1])) bad_costs(who, name[a], k, c[k]);
+        for (uint32_t k = 0; k + 1 < n; k++) {
+            const int64_t sl = ((c[k + 1] - c[k]) << 16) / (int64_t)(g->pos[k + 1] - g->pos[k]);  // operands >= 0: the quotient is the floor
+            if (sl >= (int64_t)HSPCOST_SLOPE_LIMIT) bad_costs(who, slope_name[a], k, sl);
+            slope[k] = (uint32_t)sl;
+        }
+        slope[n - 1] = n > 1 ? slope[n - 2] : 0;
+        for (uint32_t k = 0; k < HSPCOST_POINTS; k++) {
+            const uint32_t r = std::min(k, n - 1);
+            uint32_t* row = im.w + HSPCOST_ROW0 + 4 * ((uint32_t)a * HSPCOST_POINTS + k);
+            row[0] = (uint32_t)c[r];
+            row[1] = (uint32_t)((uint64_t)c[r] >> 32);
+            row[2] = slope[r];
+            row[3] = g->pos[r];
+        }
+    }
 }
 
 // One batch of trace tasks: their trace areas (trace bytes in all) and op areas (nops entries) laid out behind each other.

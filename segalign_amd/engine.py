@@ -46,6 +46,7 @@ C_ABI_SYMBOLS = [
     "sa_chain_hsps_costs", "sa_chain_hsps_all_costs", "sa_chain_gap_preset",
     "sa_stitch_chains", "sa_free_stitch",
     "sa_net_chains", "sa_free_net",
+    "sa_net_subset", "sa_free_net_subset",
 ]
 IVL_DTYPE = np.dtype([("query_start", "<u4"), ("len", "<u4")])  # struct Segment, repeat_masker_src/graph.h:32-35
 STRAND_PLUS, STRAND_MINUS, STRAND_BOTH = 1, 2, 3
@@ -142,6 +143,17 @@ class NetParams(C.Structure):
 class NetStats(C.Structure):
     _fields_ = [("chains", C.c_uint64), ("blocks", C.c_uint64), ("groups", C.c_uint64), ("fills", C.c_uint64), ("spaces", C.c_uint64),
                 ("rounds", C.c_uint64), ("max_depth", C.c_uint64), ("filled", C.c_uint64), ("prep_ms", C.c_float), ("net_ms", C.c_float)]
+
+
+SUBSET_CHAIN_DTYPE = np.dtype([("fill", "<u4"), ("chain", "<u4"), ("group", "<u4"), ("run", "<u4"), ("first_member", "<u4"),
+                               ("n_members", "<u4"), ("ref_start", "<u4"), ("ref_end", "<u4"), ("query_start", "<u4"), ("query_end", "<u4"),
+                               ("score", "<i8"), ("clipped", "<u4"), ("pad", "<u4")])  # sa_subset_chain
+SUBSET_SPLIT = 1
+
+
+class SubsetStats(C.Structure):
+    _fields_ = [("fills", C.c_uint64), ("runs", C.c_uint64), ("members", C.c_uint64), ("cut_members", C.c_uint64),
+                ("bases_rescored", C.c_uint64), ("splits", C.c_uint64), ("subset_ms", C.c_double)]
 
 
 class CallStats(C.Structure):
@@ -310,6 +322,11 @@ def lib():
     L.sa_net_chains.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(NetParams),
                                 C.POINTER(C.c_void_p), C.POINTER(NetStats)]
     L.sa_free_net.argtypes = [C.c_void_p]
+    L.sa_net_subset.restype = C.c_size_t
+    L.sa_net_subset.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                                C.c_uint32, C.POINTER(ChainParams), C.POINTER(ChainGapCosts), C.c_uint32, C.POINTER(C.c_void_p),
+                                C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(SubsetStats)]
+    L.sa_free_net_subset.argtypes = [C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -735,6 +752,38 @@ def NetChains(first, block_start, block_end, score, group=None, min_space=1, min
     res = _chain_take(out, k, NET_FILL_DTYPE)
     lib().sa_free_net(out)
     return res, _flat(st)
+
+
+def NetSubset(hsps, members, first, fills, rev, buffer=0, axis="target", split=True, diag_pen=0, anti_pen=0, gap_costs=None):
+    """Every fill of a net as sub-chains of its chain: clipped to the fill, rescored, ready for StitchChains (sa_net_subset; contract in
+    include/segalign_amd.h).  hsps, members, first: as StitchChains takes them; fills: what NetChains returned for
+    net_blocks(hsps, members, first, axis); split: cut a fill where a child lies in one of its gaps; diag_pen, anti_pen, gap_costs: the
+    penalties the chains were made under.  -> (SEG_DTYPE out_hsps, SUBSET_CHAIN_DTYPE chains, stats dict); see subset_csr."""
+    if axis not in ("target", "query"):
+        raise ValueError("axis: target or query")
+    h = np.ascontiguousarray(hsps, dtype=SEG_DTYPE)
+    m = np.ascontiguousarray(members, dtype=np.uint32)
+    f = np.ascontiguousarray(first, dtype=np.uint32)
+    fl = np.ascontiguousarray(fills, dtype=NET_FILL_DTYPE)
+    if f.size < 1 or int(f[-1]) != m.size:
+        raise ValueError("first: one offset per chain and the number of members at the end")
+    p = ChainParams(int(diag_pen), int(anti_pen), 0, 0, 0)
+    out, rec, n_out, st = C.c_void_p(), C.c_void_p(), C.c_size_t(0), SubsetStats()
+    n = lib().sa_net_subset(h.ctypes.data if h.size else None, h.size, m.ctypes.data if m.size else None, f.ctypes.data, f.size - 1,
+                            fl.ctypes.data if fl.size else None, fl.size, int(axis == "query"), int(bool(rev)), buffer, C.byref(p),
+                            None if gap_costs is None else C.byref(chain_gap_costs(gap_costs)), SUBSET_SPLIT if split else 0,
+                            C.byref(out), C.byref(n_out), C.byref(rec), C.byref(st))
+    res_h, res_c = _chain_take(out, n_out.value, SEG_DTYPE), _chain_take(rec, n, SUBSET_CHAIN_DTYPE)
+    lib().sa_free_net_subset(out, rec)
+    return res_h, res_c, _flat(st)
+
+
+def subset_csr(chains):
+    """The sub-chains of NetSubset as StitchChains and net_blocks take them, over NetSubset's out_hsps:
+    -> (members: 0 .. m - 1, first: the runs' offsets and m at the end), uint32."""
+    c = np.asarray(chains)
+    m = int(c["first_member"][-1]) + int(c["n_members"][-1]) if c.size else 0
+    return np.arange(m, dtype=np.uint32), np.concatenate([c["first_member"], [m]]).astype(np.uint32)
 
 
 def cigar(ops):

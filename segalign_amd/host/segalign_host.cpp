@@ -59,6 +59,7 @@ struct Config {  // src/graph.h:32-76 with the defaults of src/main.cpp:61-124
     uint32_t net_space = 0;   // sa_net_params.min_space; 0: the engine's default
     bool net_fill_set = false;
     uint32_t net_fill = 0;    // --gpu_net_fill=N: sa_net_params.min_fill
+    bool gpu_net_subset = false;  // --gpu_net_subset (with --gpu_net): a .net.chains file next to every .net file (sa_net_subset), with --gpu_stitch a .net.maf file
     int gap_open = 400, gap_extend = 30;
     int xdrop = 910, hspthresh = 3000, ydrop = 9430, gappedthresh = -1;
     uint32_t wga_chunk = 250000, lastz_interval = 10000000, seq_block_size = 500000000;
@@ -305,14 +306,14 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
                 sa_free_chain_all(ch, mem, nullptr, nullptr);
             }
             fclose(f);
-            if (cfg.gpu_stitch) {  // every chain as one alignment through its members, in --gpu_maf's block layout
+            // every chain of a CSR as one alignment through its members, in --gpu_maf's block layout, into the file sname
+            auto write_stitched = [&](const std::string& sname, const sa_segment_pair* sh, size_t n_sh, const uint32_t* smem, const uint32_t* sfirst,
+                                      size_t n_sc) {
                 sa_stitch_params sp = {cfg.gap_open, cfg.gap_extend, cfg.stitch_max_link, cfg.stitch_min};
                 sa_stitch_record* sr = nullptr;
                 uint32_t* sops = nullptr;
                 size_t n_sops = 0;
-                const size_t ns = sa_stitch_chains(v.data(), v.size(), idx.data(), cfirst.data(), cfirst.size() - 1, rev, buffer, &sp, &sr, &sops, &n_sops,
-                                                   nullptr, nullptr, nullptr);
-                std::string sname = base + ".stitched.maf";
+                const size_t ns = sa_stitch_chains(sh, n_sh, smem, sfirst, n_sc, rev, buffer, &sp, &sr, &sops, &n_sops, nullptr, nullptr, nullptr);
                 FILE* sf = fopen((cfg.outdir + "/" + sname).c_str(), "w");
                 if (!sf) die(7, "cant open file: %s", sname.c_str());
                 const std::string& qbuf = rev ? Qrc : Q.buf;
@@ -337,7 +338,8 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
                 }
                 fclose(sf);
                 sa_free_stitch(sr, sops, nullptr);
-            }
+            };
+            if (cfg.gpu_stitch) write_stitched(base + ".stitched.maf", v.data(), v.size(), idx.data(), cfirst.data(), cfirst.size() - 1);
             if (cfg.gpu_net) {  // which chain to believe where: the kept chains of every target record netted on the target axis
                 std::vector<uint32_t> bs(idx.size()), be(idx.size());  // a member is one block, in block coordinates
                 for (size_t k = 0; k < idx.size(); k++) {
@@ -363,6 +365,31 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
                             x.end - x.start, qn[qi].c_str(), rev ? '-' : '+', q0 - qs[qi], q1 - q0, x.chain, (long long)x.score, x.ali);
                 }
                 fclose(nfp);
+                if (cfg.gpu_net_subset) {  // every fill's part of its chain as a chain of its own, under the penalties of --gpu_chain_all
+                    sa_segment_pair* oh = nullptr;
+                    sa_subset_chain* sc = nullptr;
+                    size_t n_oh = 0;
+                    const size_t nsc = sa_net_subset(v.data(), v.size(), idx.data(), cfirst.data(), cfirst.size() - 1, nf, nn, 0, rev, buffer, &cp,
+                                                     cfg.chain_costs_set ? &cfg.chain_costs : nullptr, SA_SUBSET_SPLIT, &oh, &n_oh, &sc, nullptr);
+                    std::string sname = base + ".net.chains";
+                    f = fopen((cfg.outdir + "/" + sname).c_str(), "w");
+                    if (!f) die(7, "cant open file: %s", sname.c_str());
+                    std::vector<uint32_t> smem(n_oh), sfirst(1, 0);
+                    for (size_t k = 0; k < n_oh; k++) smem[k] = (uint32_t)k;
+                    for (size_t c = 0; c < nsc; c++) {  // the order sa_net_subset returns: by fill, then by run
+                        const sa_subset_chain& x = sc[c];
+                        const size_t r0 = x.ref_start + r_block_start, q0 = x.query_start + q_block_start;
+                        const size_t ri = chr_of(R.chr_start, r0), qi = chr_of(qs, q0);
+                        fprintf(f, "#chain %zu fill=%u run=%u score=%lld %s %zu %zu %s %zu %zu %c\n", c, x.fill, x.run, (long long)x.score,
+                                R.chr_name[ri].c_str(), r0 + 1 - R.chr_start[ri], x.ref_end + r_block_start - R.chr_start[ri], qn[qi].c_str(),
+                                q0 + 1 - qs[qi], x.query_end + q_block_start - qs[qi], rev ? '-' : '+');
+                        for (size_t k = x.first_member; k < (size_t)x.first_member + x.n_members; k++) emit(oh[k]);
+                        sfirst.push_back(x.first_member + x.n_members);
+                    }
+                    fclose(f);
+                    if (cfg.gpu_stitch) write_stitched(base + ".net.maf", oh, n_oh, smem.data(), sfirst.data(), nsc);
+                    sa_free_net_subset(oh, sc);
+                }
                 sa_free_net(nf);
             }
             std::sort(idx.begin(), idx.end());  // an HSP is a member of one chain at most: no duplicates
@@ -474,7 +501,11 @@ static void usage() {
             "      on the target best first, each filling what is still open, the gaps inside a fill open to lower chains one level down; a\n"
             "      line 'net <target record> <length>' per record, then per fill, indented by its depth, 'fill <tstart> <tsize> <qname> <+|->\n"
             "      <qstart> <qsize> chain=<k> score=<s> ali=<n>'; open stretches shorter than min_space, default 1, are not searched)\n"
-            "  --gpu_net_fill=N (with --gpu_net: a chain fills an open stretch only with at least N bases in it; default 1)\n");
+            "  --gpu_net_fill=N (with --gpu_net: a chain fills an open stretch only with at least N bases in it; default 1)\n"
+            "  --gpu_net_subset (with --gpu_net: a .net.chains file next to each .net file: every fill's part of its chain as a chain of its\n"
+            "      own, cut where a lower chain fills one of its gaps, clipped members rescored, under the penalties of --gpu_chain_all and\n"
+            "      --gpu_chain_costs; per sub-chain a line `#chain k fill=F run=R score=S` with its target and query extents, then its members\n"
+            "      as .segments lines; with --gpu_stitch also a .net.maf file: those sub-chains stitched, in the .stitched.maf layout)\n");
 }
 
 // A gap-cost table in axtChain's linearGap layout (see usage).  The file's form is checked here; the values are checked again by the
@@ -617,6 +648,7 @@ int main(int argc, char** argv) {
             cfg.gpu_net = true;
             cfg.net_space = (uint32_t)ms;
         }
+        else if (!strcmp(a, "--gpu_net_subset")) cfg.gpu_net_subset = true;
         else if (opt(a, "--gpu_net_fill", v)) {
             char* endp = nullptr;
             const long long mf = strtoll(v.c_str(), &endp, 10);
@@ -640,6 +672,7 @@ int main(int argc, char** argv) {
     if (cfg.gpu_stitch && !cfg.gpu_chain && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_stitch needs --gpu_chain or --gpu_chain_all\n"); return 1; }
     if (cfg.stitch_min_set && !cfg.gpu_stitch) { fprintf(stderr, "--gpu_stitch_min needs --gpu_stitch\n"); return 1; }
     if (cfg.gpu_net && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_net needs --gpu_chain_all\n"); return 1; }
+    if (cfg.gpu_net_subset && !cfg.gpu_net) { fprintf(stderr, "--gpu_net_subset needs --gpu_net and --gpu_chain_all\n"); return 1; }
     if (cfg.net_fill_set && !cfg.gpu_net) { fprintf(stderr, "--gpu_net_fill needs --gpu_net and --gpu_chain_all\n"); return 1; }
     cfg.target = pos[0];
     cfg.query = pos[1];

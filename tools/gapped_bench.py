@@ -33,9 +33,13 @@ With --net [--net-space N] [--net-fill N] (which implies --chain-all) the kept c
 (DESIGN.md 19): the line then adds the chains and blocks, fills, rounds, spaces searched, max depth, chains without a fill, prep ms and
 net ms beside peel ms and the DP's kernel ms.  The fills are checked against the model (tests/net_model.py) once per run.
 
+With --net-subset (which implies --net) the fills go through sa_net_subset with the split flag, under --chain-pen: the
+line then adds fills, runs, members, cut members, bases rescored, the output bytes and subset ms beside net ms and peel ms.  Output HSPs
+and sub-chains are checked against the model (tests/net_subset_model.py) once per run.
+
   python tools/gapped_bench.py [--workloads standin,lumpy] [--repeat 3] [--align] [--greedy] [--batches 1024,2048,...]
                                [--pieces N] [--max-extent M] [--chain] [--chain-pen D,A] [--chain-costs T] [--chain-all] [--chain-min N] [--stitch] [--stitch-max-link N]
-                               [--net] [--net-space N] [--net-fill N]
+                               [--net] [--net-space N] [--net-fill N] [--net-subset]
 """
 import argparse
 import functools
@@ -205,8 +209,37 @@ def stitch_fields(hsps, members, repeat, max_link):
             "kept_gapped_alignments": int(grecs.size), "stitch_model_checked": True, "stitch_model_s": round(model_s, 1)}
 
 
-def net_fields(hsps, chains, members, repeat, net, peel_ms, dp_ms):
-    """sa_net_chains on the kept chains' target blocks, the run with the least net time, checked against the model."""
+def subset_fields(hsps, mem, first, fills, repeat, pen, net_ms, peel_ms):
+    """sa_net_subset on the fills of the net, the run with the least subset time, checked against the model."""
+    import net_subset_model as NS
+    best = None
+    for _ in range(repeat):
+        t0 = time.perf_counter()
+        # the penalties must be the chains': chain_all_fields calls ChainHspsAll under pen without a gap-cost table, so none is given here;
+        # should --chain-costs ever reach ChainHspsAll, the same table belongs here and in the model call below
+        r = E.NetSubset(hsps, mem, first, fills, False, 0, axis="target", split=True, diag_pen=pen[0], anti_pen=pen[1])
+        wall = (time.perf_counter() - t0) * 1e3
+        if best is None or r[2]["subset_ms"] < best[0][2]["subset_ms"]:
+            best = (r, wall)
+    (out, sub, st), wall = best
+    t0 = time.perf_counter()
+    want_h, want_c, want_st = NS.subset(E.copy_ref_codes(), E.copy_query_codes(0, False), SUB, hsps, mem, first, fills, diag_pen=pen[0],
+                                        anti_pen=pen[1])
+    model_s = time.perf_counter() - t0
+    if not (np.array_equal(out, want_h.astype(out.dtype)) and np.array_equal(sub, want_c.astype(sub.dtype))
+            and all(st[k] == want_st[k] for k in NS.COUNTS)):
+        raise SystemExit("sa_net_subset differs from the model")
+    return {"subset_fills": int(st["fills"]), "subset_runs": int(st["runs"]), "subset_members": int(st["members"]),
+            "subset_cut_members": int(st["cut_members"]), "subset_bases_rescored": int(st["bases_rescored"]), "subset_splits": int(st["splits"]),
+            "subset_out_bytes": int(out.nbytes + sub.nbytes), "subset_ms": round(st["subset_ms"], 3), "subset_net_ms": round(net_ms, 3),
+            "subset_peel_ms": round(peel_ms, 3), "subset_call_ms": round(wall, 3),
+            "subset_over_net": round(st["subset_ms"] / net_ms, 4) if net_ms > 0 else None, "subset_model_checked": True,
+            "subset_model_s": round(model_s, 1)}
+
+
+def net_fields(hsps, chains, members, repeat, net, peel_ms, dp_ms, pen=(0, 0)):
+    """sa_net_chains on the kept chains' target blocks, the run with the least net time, checked against the model; net[2]: also
+    subset_fields on its fills."""
     import net_model as N
     mem, first = E.chain_csr(members)
     bs, be = E.net_blocks(hsps, mem, first, axis="target")
@@ -223,7 +256,8 @@ def net_fields(hsps, chains, members, repeat, net, peel_ms, dp_ms):
     model_s = time.perf_counter() - t0
     if not np.array_equal(fills, want.astype(fills.dtype)) or any(st[k] != want_st[k] for k in ("fills", "filled", "max_depth")):
         raise SystemExit("sa_net_chains differs from the model")
-    return {"net_min_space": int(net[0]), "net_min_fill": int(net[1]), "net_chains": int(st["chains"]), "net_blocks": int(st["blocks"]),
+    extra = subset_fields(hsps, mem, first, fills, repeat, pen, st["net_ms"], peel_ms) if len(net) > 2 and net[2] else {}
+    return {**extra, "net_min_space": int(net[0]), "net_min_fill": int(net[1]), "net_chains": int(st["chains"]), "net_blocks": int(st["blocks"]),
             "net_fills": int(st["fills"]), "net_rounds": int(st["rounds"]), "net_spaces": int(st["spaces"]), "net_max_depth": int(st["max_depth"]),
             "net_chains_without_fill": int(st["chains"] - st["filled"]), "net_prep_ms": round(st["prep_ms"], 3), "net_ms": round(st["net_ms"], 3),
             "net_call_ms": round(wall, 3), "net_over_peel": round(st["net_ms"] / peel_ms, 4) if peel_ms > 0 else None,
@@ -255,7 +289,7 @@ def chain_all_fields(hsps, repeat, pen, min_score, dp, align, greedy, stitch=Non
     if stitch is not None:
         out.update(stitch_fields(hsps, members, repeat, stitch))
     if net is not None:
-        out.update(net_fields(hsps, chains, members, repeat, net, st["peel_ms"], st["kernel_ms"]))
+        out.update(net_fields(hsps, chains, members, repeat, net, st["peel_ms"], st["kernel_ms"], pen))
     return out
 
 
@@ -401,7 +435,9 @@ def main():
     ap.add_argument("--net", action="store_true", help="also net the kept chains on the target axis (sa_net_chains); implies --chain-all")
     ap.add_argument("--net-space", type=int, default=1, help="with --net: min_space")
     ap.add_argument("--net-fill", type=int, default=1, help="with --net: min_fill")
+    ap.add_argument("--net-subset", action="store_true", help="also cut the fills into sub-chains (sa_net_subset); implies --net")
     a = ap.parse_args()
+    a.net = a.net or a.net_subset
     a.chain_all = a.chain_all or a.stitch or a.net
     chain = tuple(int(x) for x in a.chain_pen.split(",")) if a.chain or a.chain_all else None
     if a.chain_costs and chain is None:
@@ -411,7 +447,7 @@ def main():
     for name in a.workloads.split(","):
         if not a.batches:
             print(json.dumps(run(name, a.repeat, a.align, a.greedy, pieces=a.pieces, chain=chain, chain_all_min=a.chain_min if a.chain_all else None,
-                                 stitch=a.stitch_max_link if a.stitch else None, net=(a.net_space, a.net_fill) if a.net else None,
+                                 stitch=a.stitch_max_link if a.stitch else None, net=(a.net_space, a.net_fill, a.net_subset) if a.net else None,
                                  chain_costs=a.chain_costs or None)), flush=True)
             continue
         for b in a.batches.split(","):
