@@ -1110,6 +1110,107 @@ size_t sa_net_subset(const sa_segment_pair* hsps, size_t n_hsps, const uint32_t*
                      sa_subset_stats* stats);
 void sa_free_net_subset(sa_segment_pair* out_hsps, sa_subset_chain* chains);
 
+/* ---- classifying the fills of a net and counting duplication on the other axis (additive; restated by
+ * tests/net_class_model.py) ----------
+ *
+ * sa_net_classify says, for every fill of a net, where it lands on the OTHER axis relative to its parent and how much of what it claims
+ * there is claimed by another fill too, and marks the fills a synteny filter keeps.  It is the project's own contract in the spirit of
+ * UCSC's netSyntenic followed by netFilter -syn (not claimed to equal them).  Below, "axis" is the axis the net was made on and
+ * "other" the other one.  The entry reads no sequence and no table: it needs sa_initialize_interface only.
+ *   Input: the CSR blocks of the netted axis exactly as sa_net_chains took them, first[n_chains + 1], block_start[], block_end[]; the
+ *     same blocks on the other axis, oblock_start[], oblock_end[], parallel arrays with the same indices; ogroup[n_chains] (NULL: all
+ *     0), the sequence a chain lies on on the other axis (in the host a query record); ostrand[n_chains] (uint8 0 / 1, NULL: all 0);
+ *     fills[n_fills], the output of one sa_net_chains call on those blocks; p: the filter's thresholds (NULL: all 0, read only with
+ *     the flag); flags: SA_NETCLASS_FILTER or 0.
+ *   Other-axis coordinates are given in one common orientation per ogroup, every one < 2^31.  The other blocks of a chain with ostrand
+ *     0 ascend and are disjoint (oend_k <= ostart_k+1); those of a chain with ostrand 1 descend and are disjoint (oend_k+1 <=
+ *     ostart_k): the caller has flipped a minus-strand chain into the plus orientation.  Every block is as long on the other axis as on
+ *     the axis, a block being ungapped.
+ *   Validation (on the host, one linear pass; a message and exit code 1, like the other entries): the CSR and block rules of
+ *     sa_net_chains (first[0] = 0, first[] non-decreasing, at most 4 194 304 chains and 1 << 26 blocks, start < end < 2^31, the blocks of
+ *     a chain ascend and are disjoint); on the other axis ostart < oend < 2^31, oend - ostart = end - start, and the order rule above;
+ *     ostrand in 0 .. 1; for every fill start < end, chain < n_chains, n_blocks >= 1, first[chain] <= first_block and first_block +
+ *     n_blocks <= first[chain + 1], its first block ends after start and its last block starts before end, parent is -1 or an earlier
+ *     index, and depth is 0 without a parent and the parent's depth + 1 with one (what bounds the device's walk to the root); at most
+ *     2^31 - 1 fills and 1 << 26 clipped blocks (the sum of n_blocks); min_size, min_ali and max_far at most 1 << 31; flags <= 1.
+ *   Clipped other block: block k of a fill cut to [start, end) on the axis loses dL bases on its left and dR on its right there; its
+ *     other interval is [ostart_k + dL, oend_k - dR) with ostrand 0 and [ostart_k + dR, oend_k - dL) with ostrand 1.
+ *   Other hull of a fill: ostart = the least start and oend = the greatest end of its clipped other blocks; by monotonicity the first
+ *     block's start and the last block's end with ostrand 0, the last block's start and the first block's end with ostrand 1.
+ *   Class (type): parent = -1 -> top (0), oover = ofar = 0.  Otherwise, if the fill's ogroup differs from the parent fill's -> nonSyn
+ *     (3), oover = ofar = 0.  Otherwise x = min(oend, parent's oend) - max(ostart, parent's ostart) in int64, the parent's hull being
+ *     that of the whole parent fill; x > 0: oover = x, ofar = 0; else oover = 0, ofar = -x; the class is syn (1) when the two chains'
+ *     ostrand are equal and inv (2) when they differ.
+ *   Duplication: odup = the number of bases of the fill's clipped other blocks whose depth is >= 2, depth being counted over the clipped
+ *     other blocks of ALL fills of the call with the same ogroup, the fill's own included, and of every net group: duplication is a
+ *     property of the other sequence, not of one group of the net.  Intervals are half-open; abutting blocks share no base.
+ *     Consequence: 0 <= odup <= the fill's clipped bases (ali as sa_net_chains returned it).
+ *   Filter (with SA_NETCLASS_FILTER): self(f) = score >= min_score and end - start >= min_size and ali >= min_ali and the class test;
+ *     the class test is score >= min_top_score for top, false for nonSyn, ofar <= max_far for syn and inv.  keep(f) = self(f) and
+ *     keep(parent): a dropped fill takes its whole subtree with it.  Without the flag every keep is 1.  score, ali and depth are the
+ *     fields of the fill as given.
+ *   Output: one sa_net_class per fill, in the fills' order; strand is the chain's ostrand, ogroup the chain's.
+ * The device lays the clipped other blocks out by a prefix sum, writes two events per block keyed (ogroup, coordinate, is_start), sorts
+ * them once, takes the depth after every event from a prefix count of the starts, the duplicated length before every event from a
+ * second prefix sum, and per block and per fill the difference of two prefix values; class and keep are one thread per fill (DESIGN.md
+ * 22).  Slots and thread safety are those of sa_net_chains. */
+#define SA_NETCLASS_FILTER 1u /* apply the thresholds of sa_net_class_params; without it every keep is 1 */
+#define SA_NETCLASS_TOP 0
+#define SA_NETCLASS_SYN 1
+#define SA_NETCLASS_INV 2
+#define SA_NETCLASS_NONSYN 3
+
+typedef struct sa_net_class_params { /* 32 bytes */
+    int64_t min_score;     /* every fill: score >= min_score */
+    int64_t min_top_score; /* a top fill: score >= min_top_score */
+    uint32_t min_size;     /* end - start >= min_size; at most 1 << 31 */
+    uint32_t min_ali;      /* ali >= min_ali; at most 1 << 31 */
+    uint32_t max_far;      /* a syn or inv fill: ofar <= max_far; at most 1 << 31 */
+    uint32_t pad;
+} sa_net_class_params;
+
+typedef struct sa_net_class { /* 32 bytes */
+    uint32_t ostart, oend; /* the hull of the clipped other blocks */
+    uint32_t oover;        /* bases the hull shares with the parent's hull */
+    uint32_t ofar;         /* distance between the two hulls when they share none */
+    uint32_t odup;         /* bases of the clipped other blocks with depth >= 2 */
+    uint32_t ogroup;
+    uint8_t type;          /* SA_NETCLASS_TOP, _SYN, _INV, _NONSYN */
+    uint8_t strand;        /* the chain's ostrand */
+    uint8_t keep;
+    uint8_t pad;
+    uint32_t pad2;
+} sa_net_class;
+
+typedef struct sa_net_class_stats { /* 88 bytes */
+    uint64_t fills;
+    uint64_t blocks;     /* clipped blocks */
+    uint64_t events;     /* two per clipped block */
+    uint64_t ogroups;    /* distinct ogroup values among the fills */
+    uint64_t n_type[4];  /* fills per class */
+    uint64_t kept;
+    uint64_t dup_bases;  /* the sum of odup */
+    float class_ms;      /* device time of all kernels */
+    uint32_t pad;
+} sa_net_class_stats;
+#ifdef __cplusplus
+static_assert(sizeof(sa_net_class_params) == 32, "sa_net_class_params is 32 bytes");
+static_assert(sizeof(sa_net_class) == 32, "sa_net_class is 32 bytes");
+static_assert(sizeof(sa_net_class_stats) == 88, "sa_net_class_stats is 88 bytes");
+#else
+_Static_assert(sizeof(sa_net_class_params) == 32, "sa_net_class_params is 32 bytes");
+_Static_assert(sizeof(sa_net_class) == 32, "sa_net_class is 32 bytes");
+_Static_assert(sizeof(sa_net_class_stats) == 88, "sa_net_class_stats is 88 bytes");
+#endif
+
+/* Returns the number of records, n_fills.  *classes is malloc-ed and released with sa_free_net_class; it is NULL when there are none.
+ * ogroup, ostrand, p, stats: nullable. */
+size_t sa_net_classify(const uint32_t* first, const uint32_t* block_start, const uint32_t* block_end, const uint32_t* oblock_start,
+                       const uint32_t* oblock_end, const uint32_t* ogroup, const uint8_t* ostrand, size_t n_chains,
+                       const sa_net_fill* fills, size_t n_fills, const sa_net_class_params* p, uint32_t flags, sa_net_class** classes,
+                       sa_net_class_stats* stats);
+void sa_free_net_class(sa_net_class* classes);
+
 const char* sa_version(void);
 
 #ifdef __cplusplus

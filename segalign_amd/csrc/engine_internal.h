@@ -16,7 +16,8 @@
 //   api_stitch.hip     sa_stitch_chains: every chain of HSPs as one gapped alignment through its members (stitch.hip, gapped.hip's walk)
 //   api_net.hip        sa_net_chains: the chains of every group netted into fills and gaps on one axis (net.hip)
 //   api_netsubset.hip  sa_net_subset: the fills of a net cut into clipped, rescored sub-chains (netsubset.hip)
-//   post_host.h        what those five share on the host: event timing, checked launches, buffer carving, caller-owned arrays, trace batches
+//   api_netclass.hip   sa_net_classify: the fills of a net classed against their parents on the other axis, with duplication and the filter (netclass.hip)
+//   post_host.h        what those six share on the host: event timing, checked launches, buffer carving, caller-owned arrays, trace batches
 //   gapped.hip         kernels of the gapped entries: y-drop extension of a side, trace sweep, path walk (gapped.h)
 //   cover.hip          kernels and rocPRIM steps of the greedy cover index; its sort and scan wrappers also serve api_hspchain.hip (gapped.h)
 //   hspchain.hip       kernels of the chaining DP: rank keys, gather, tile cross / resolve, group ends, members, nodes (hspchain.h)
@@ -25,6 +26,7 @@
 //   stitch.hip         kernels of the stitch: member scores, the global sweep of a link in five instances (stitch.h)
 //   net.hip            kernels of the net: priority order, hulls, and a round's search, count and emit, one wavefront per space (net.h)
 //   netsubset.hip      kernels of the net subset: cut marks, clipped members, the cut members' scores, run sums and records (netsubset.h)
+//   netclass.hip       kernels of the net classes: clipped other blocks as sorted events, depth and duplicated length by prefix sums, class, keep (netclass.h)
 //   api_introspect.hip statistics, lookup mode, copies of device state for the tests
 #pragma once
 #include <hip/hip_runtime.h>
@@ -360,6 +362,7 @@ struct Slot {
     // final order's keys; all fills in emission order (grown with their contents kept); this round's spaces and the next one's
     DevBuf<uint8_t> net_work, net_round, net_fills, net_space[2];
     DevBuf<uint8_t> netsubset;        // sa_net_subset (api_netsubset.hip, netsubset.hip): the fills, the members' HSPs and everything made of them
+    DevBuf<uint8_t> netclass;         // sa_net_classify (api_netclass.hip, netclass.hip): the fills, the blocks of both axes, the events and everything made of them
     bool early = false;               // taken from the pool that serves sa_chain_hsps before InitializeProcessor (pool.hip)
 };
 

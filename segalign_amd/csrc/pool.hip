@@ -138,6 +138,7 @@ void slot_destroy(Slot& s) {
     s.net_fills.release("net fills");
     for (int i = 0; i < 2; i++) s.net_space[i].release("net spaces");
     s.netsubset.release("net subset");
+    s.netclass.release("net class");
     s.cand_list.release("candidate list");
     s.l2_list.release("second-level list");
     s.audit.release("audit list");

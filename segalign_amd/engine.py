@@ -47,6 +47,7 @@ C_ABI_SYMBOLS = [
     "sa_stitch_chains", "sa_free_stitch",
     "sa_net_chains", "sa_free_net",
     "sa_net_subset", "sa_free_net_subset",
+    "sa_net_classify", "sa_free_net_class",
 ]
 IVL_DTYPE = np.dtype([("query_start", "<u4"), ("len", "<u4")])  # struct Segment, repeat_masker_src/graph.h:32-35
 STRAND_PLUS, STRAND_MINUS, STRAND_BOTH = 1, 2, 3
@@ -154,6 +155,24 @@ SUBSET_SPLIT = 1
 class SubsetStats(C.Structure):
     _fields_ = [("fills", C.c_uint64), ("runs", C.c_uint64), ("members", C.c_uint64), ("cut_members", C.c_uint64),
                 ("bases_rescored", C.c_uint64), ("splits", C.c_uint64), ("subset_ms", C.c_double)]
+
+
+NET_CLASS_DTYPE = np.dtype([("ostart", "<u4"), ("oend", "<u4"), ("oover", "<u4"), ("ofar", "<u4"), ("odup", "<u4"), ("ogroup", "<u4"),
+                            ("type", "u1"), ("strand", "u1"), ("keep", "u1"), ("pad", "u1"), ("pad2", "<u4")])  # sa_net_class
+NETCLASS_FILTER = 1
+NETCLASS_TOP, NETCLASS_SYN, NETCLASS_INV, NETCLASS_NONSYN = 0, 1, 2, 3
+NETCLASS_NAMES = ("top", "syn", "inv", "nonSyn")
+NETCLASS_THRESHOLDS = ("min_score", "min_top_score", "min_size", "min_ali", "max_far")
+
+
+class NetClassParams(C.Structure):
+    _fields_ = [("min_score", C.c_int64), ("min_top_score", C.c_int64), ("min_size", C.c_uint32), ("min_ali", C.c_uint32),
+                ("max_far", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class NetClassStats(C.Structure):
+    _fields_ = [("fills", C.c_uint64), ("blocks", C.c_uint64), ("events", C.c_uint64), ("ogroups", C.c_uint64), ("n_type", C.c_uint64 * 4),
+                ("kept", C.c_uint64), ("dup_bases", C.c_uint64), ("class_ms", C.c_float), ("pad", C.c_uint32)]
 
 
 class CallStats(C.Structure):
@@ -327,6 +346,10 @@ def lib():
                                 C.c_uint32, C.POINTER(ChainParams), C.POINTER(ChainGapCosts), C.c_uint32, C.POINTER(C.c_void_p),
                                 C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(SubsetStats)]
     L.sa_free_net_subset.argtypes = [C.c_void_p, C.c_void_p]
+    L.sa_net_classify.restype = C.c_size_t
+    L.sa_net_classify.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                  C.c_size_t, C.POINTER(NetClassParams), C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(NetClassStats)]
+    L.sa_free_net_class.argtypes = [C.c_void_p]
     _lib = L
     return L
 
@@ -784,6 +807,81 @@ def subset_csr(chains):
     c = np.asarray(chains)
     m = int(c["first_member"][-1]) + int(c["n_members"][-1]) if c.size else 0
     return np.arange(m, dtype=np.uint32), np.concatenate([c["first_member"], [m]]).astype(np.uint32)
+
+
+def net_other_blocks(hsps, members, first, axis="target", strand=None, size=None):
+    """net_blocks on the OTHER axis than `axis`, as NetClassify takes it.  strand: one 0 / 1 per chain (None: all 0); for a chain with
+    strand 1 every block [s, e) becomes [size[chain] - e, size[chain] - s), the flip of a minus-strand chain into the plus orientation,
+    so that its blocks descend.  size: one length per chain (that of the sequence the chain lies on), needed with strand.
+    -> (oblock_start, oblock_end), uint32."""
+    if axis not in ("target", "query"):
+        raise ValueError("axis: target or query")
+    s, e = net_blocks(hsps, members, first, "query" if axis == "target" else "target")
+    if strand is None:
+        return s, e
+    f = np.asarray(first, dtype=np.int64)
+    st = np.asarray(strand, dtype=np.uint8)
+    if size is None or st.size != f.size - 1 or np.asarray(size).size != st.size:
+        raise ValueError("strand, size: one entry per chain")
+    chain = np.repeat(np.arange(st.size), np.diff(f))
+    flip = st[chain] != 0
+    n = np.asarray(size, dtype=np.int64)[chain]
+    if np.any(flip & (e.astype(np.int64) > n)):
+        raise ValueError("size: a block of a strand-1 chain ends past it")
+    os_ = np.where(flip, n - e.astype(np.int64), s.astype(np.int64))
+    oe = np.where(flip, n - s.astype(np.int64), e.astype(np.int64))
+    return os_.astype(np.uint32), oe.astype(np.uint32)
+
+
+def NetClassify(first, block_start, block_end, oblock_start, oblock_end, fills, ogroup=None, ostrand=None, filter=None):
+    """Every fill of a net classed against its parent on the other axis (top / syn / inv / nonSyn), with the bases it shares with other
+    fills there and the synteny filter's keep mark (sa_net_classify; contract in include/segalign_amd.h).
+    first, block_start, block_end: what NetChains took; oblock_start, oblock_end: the same blocks on the other axis (net_other_blocks);
+    fills: what NetChains returned; ogroup: one uint32 per chain, the sequence it lies on on the other axis (None: all 0); ostrand: one
+    0 / 1 per chain (None: all 0); filter: a dict of min_score, min_top_score, min_size, min_ali, max_far (missing ones 0), or None for
+    no filter.  -> (NET_CLASS_DTYPE classes, stats dict).  Needs InitializeInterface only."""
+    f = np.ascontiguousarray(first, dtype=np.uint32)
+    arr = [np.ascontiguousarray(x, dtype=np.uint32) for x in (block_start, block_end, oblock_start, oblock_end)]
+    fl = np.ascontiguousarray(fills, dtype=NET_FILL_DTYPE)
+    g = None if ogroup is None else np.ascontiguousarray(ogroup, dtype=np.uint32)
+    sd = None if ostrand is None else np.ascontiguousarray(ostrand, dtype=np.uint8)
+    n = f.size - 1
+    if n < 0 or any(x.size != arr[0].size for x in arr) or arr[0].size < int(f.max()) or any(x is not None and x.size != n for x in (g, sd)):
+        raise ValueError("first: one offset per chain and one more; ogroup, ostrand: one entry per chain; blocks: first[-1] of each, on both axes")
+    p = NetClassParams()
+    if filter is not None:
+        if set(filter) - set(NETCLASS_THRESHOLDS):
+            raise ValueError("filter: %s" % ", ".join(NETCLASS_THRESHOLDS))
+        for k in NETCLASS_THRESHOLDS:
+            setattr(p, k, int(filter.get(k, 0)))
+    out, st = C.c_void_p(), NetClassStats()
+    ptr = [x.ctypes.data if x.size else None for x in arr]
+    k = lib().sa_net_classify(f.ctypes.data, ptr[0], ptr[1], ptr[2], ptr[3], g.ctypes.data if g is not None and n else None,
+                              sd.ctypes.data if sd is not None and n else None, n, fl.ctypes.data if fl.size else None, fl.size,
+                              C.byref(p), NETCLASS_FILTER if filter is not None else 0, C.byref(out), C.byref(st))
+    res = _chain_take(out, k, NET_CLASS_DTYPE)
+    lib().sa_free_net_class(out)
+    stats = _flat(st)
+    stats["n_type"] = [int(x) for x in st.n_type]
+    return res, stats
+
+
+def net_select(fills, keep):
+    """The fills with keep != 0, in the same order, parent remapped to the new indices: -> (fills', index of every kept fill in the
+    input).  keep must be closed under subtrees (NetClassify's is): a kept fill's parent is kept, so the result is a net of its own that
+    NetSubset takes unchanged."""
+    fl = np.ascontiguousarray(fills, dtype=NET_FILL_DTYPE)
+    k = np.asarray(keep).astype(bool)
+    if k.shape != fl.shape:
+        raise ValueError("keep: one entry per fill")
+    index = np.flatnonzero(k)
+    new = np.cumsum(k) - 1
+    out = fl[index].copy()
+    has = out["parent"] >= 0
+    if np.any(~k[out["parent"][has]]):
+        raise ValueError("keep: a kept fill whose parent is dropped")
+    out["parent"][has] = new[out["parent"][has]]
+    return out, index.astype(np.uint32)
 
 
 def cigar(ops):

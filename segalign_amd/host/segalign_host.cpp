@@ -59,6 +59,9 @@ struct Config {  // src/graph.h:32-76 with the defaults of src/main.cpp:61-124
     uint32_t net_space = 0;   // sa_net_params.min_space; 0: the engine's default
     bool net_fill_set = false;
     uint32_t net_fill = 0;    // --gpu_net_fill=N: sa_net_params.min_fill
+    bool gpu_net_class = false;   // --gpu_net_class (with --gpu_net): a .net.class file next to every .net file (sa_net_classify, the query as the other axis)
+    bool net_syn = false;         // --gpu_net_syn=...: the synteny filter's thresholds; .net.class and --gpu_net_subset take the kept fills only
+    sa_net_class_params net_syn_p = {0, 0, 0, 0, 0, 0};
     bool gpu_net_subset = false;  // --gpu_net_subset (with --gpu_net): a .net.chains file next to every .net file (sa_net_subset), with --gpu_stitch a .net.maf file
     int gap_open = 400, gap_extend = 30;
     int xdrop = 910, hspthresh = 3000, ydrop = 9430, gappedthresh = -1;
@@ -276,6 +279,7 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
             std::vector<uint32_t> idx, cfirst(1, 0);  // cfirst: the chains' offsets into the members, for --gpu_stitch and --gpu_net
             std::vector<int64_t> cscore;              // with --gpu_net: every kept chain's score and the target record of its pair
             std::vector<uint32_t> ctarget;
+            std::vector<uint32_t> cquery;             // with --gpu_net_class: the query record of its pair
             if (cfg.gpu_chain) {
                 sa_chain_member* mem = nullptr;
                 const size_t nm = cfg.chain_costs_set ? sa_chain_hsps_costs(v.data(), v.size(), group.data(), &cp, &cfg.chain_costs, &mem, nullptr, nullptr)
@@ -301,6 +305,7 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
                     if (cfg.gpu_net) {
                         cscore.push_back(ch[c].score);
                         ctarget.push_back((uint32_t)(pairs[ch[c].group] >> 32));
+                        cquery.push_back((uint32_t)pairs[ch[c].group]);
                     }
                 }
                 sa_free_chain_all(ch, mem, nullptr, nullptr);
@@ -349,13 +354,33 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
                 sa_net_params np = {cfg.net_space, cfg.net_fill};
                 sa_net_fill* nf = nullptr;
                 const size_t nn = sa_net_chains(cfirst.data(), bs.data(), be.data(), cscore.data(), ctarget.data(), cfirst.size() - 1, &np, &nf, nullptr);
+                // where every fill lands on the query relative to its parent, and what it shares there with other fills; a
+                // file holds one strand, so every chain has ostrand 0 and the coordinates go in as they are
+                sa_net_class* ncl = nullptr;
+                FILE* cfp = nullptr;
+                if (cfg.gpu_net_class) {
+                    std::vector<uint32_t> obs(idx.size()), obe(idx.size());
+                    for (size_t k = 0; k < idx.size(); k++) {
+                        obs[k] = v[idx[k]].query_start;
+                        obe[k] = v[idx[k]].query_start + v[idx[k]].len + 1;
+                    }
+                    sa_net_classify(cfirst.data(), bs.data(), be.data(), obs.data(), obe.data(), cquery.data(), nullptr, cfirst.size() - 1, nf, nn,
+                                    cfg.net_syn ? &cfg.net_syn_p : nullptr, cfg.net_syn ? SA_NETCLASS_FILTER : 0, &ncl, nullptr);
+                    std::string class_name = base + ".net.class";
+                    cfp = fopen((cfg.outdir + "/" + class_name).c_str(), "w");
+                    if (!cfp) die(7, "cant open file: %s", class_name.c_str());
+                }
+                bool class_head = false;  // this record's net line stands in the .net.class file
                 std::string nname = base + ".net";
                 FILE* nfp = fopen((cfg.outdir + "/" + nname).c_str(), "w");
                 if (!nfp) die(7, "cant open file: %s", nname.c_str());
                 for (size_t k = 0; k < nn; k++) {  // the order sa_net_chains returns: by target record, then the pre-order walk of its net
                     const sa_net_fill& x = nf[k];
                     const size_t ri = x.group;
-                    if (k == 0 || nf[k - 1].group != x.group) fprintf(nfp, "net %s %u\n", R.chr_name[ri].c_str(), R.chr_len[ri]);
+                    if (k == 0 || nf[k - 1].group != x.group) {
+                        fprintf(nfp, "net %s %u\n", R.chr_name[ri].c_str(), R.chr_len[ri]);
+                        class_head = false;
+                    }
                     // an HSP is ungapped: a clip on the target shifts the query by the same amount
                     const uint32_t k0 = x.first_block, k1 = x.first_block + x.n_blocks - 1;
                     const size_t q0 = (size_t)v[idx[k0]].query_start + (x.start - bs[k0]) + q_block_start;
@@ -363,13 +388,38 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
                     const size_t qi = chr_of(qs, q0);
                     fprintf(nfp, "%*sfill %zu %u %s %c %zu %zu chain=%u score=%lld ali=%u\n", (int)x.depth, "", x.start + r_block_start - R.chr_start[ri],
                             x.end - x.start, qn[qi].c_str(), rev ? '-' : '+', q0 - qs[qi], q1 - q0, x.chain, (long long)x.score, x.ali);
+                    if (cfp && ncl[k].keep) {  // the same line and the class; a record's net line before its first kept fill
+                        static const char* const type_name[4] = {"top", "syn", "inv", "nonSyn"};
+                        if (!class_head) fprintf(cfp, "net %s %u\n", R.chr_name[ri].c_str(), R.chr_len[ri]);
+                        class_head = true;
+                        fprintf(cfp, "%*sfill %zu %u %s %c %zu %zu chain=%u score=%lld ali=%u type=%s qover=%u qfar=%u qdup=%u\n", (int)x.depth, "",
+                                x.start + r_block_start - R.chr_start[ri], x.end - x.start, qn[qi].c_str(), rev ? '-' : '+', q0 - qs[qi], q1 - q0, x.chain,
+                                (long long)x.score, x.ali, type_name[ncl[k].type & 3], ncl[k].oover, ncl[k].ofar, ncl[k].odup);
+                    }
                 }
                 fclose(nfp);
+                if (cfp) fclose(cfp);
+                std::vector<sa_net_fill> kept_fills;  // with --gpu_net_syn: the kept fills as a net of their own, parents renumbered
+                const sa_net_fill* sub_fills = nf;
+                size_t n_sub_fills = nn;
+                if (cfg.net_syn) {
+                    std::vector<int32_t> renum(nn, -1);
+                    for (size_t k = 0; k < nn; k++) {
+                        if (!ncl[k].keep) continue;
+                        sa_net_fill x = nf[k];
+                        if (x.parent >= 0) x.parent = renum[x.parent];  // keep is closed under subtrees: the parent is kept
+                        renum[k] = (int32_t)kept_fills.size();
+                        kept_fills.push_back(x);
+                    }
+                    sub_fills = kept_fills.data();
+                    n_sub_fills = kept_fills.size();
+                }
+                sa_free_net_class(ncl);
                 if (cfg.gpu_net_subset) {  // every fill's part of its chain as a chain of its own, under the penalties of --gpu_chain_all
                     sa_segment_pair* oh = nullptr;
                     sa_subset_chain* sc = nullptr;
                     size_t n_oh = 0;
-                    const size_t nsc = sa_net_subset(v.data(), v.size(), idx.data(), cfirst.data(), cfirst.size() - 1, nf, nn, 0, rev, buffer, &cp,
+                    const size_t nsc = sa_net_subset(v.data(), v.size(), idx.data(), cfirst.data(), cfirst.size() - 1, sub_fills, n_sub_fills, 0, rev, buffer, &cp,
                                                      cfg.chain_costs_set ? &cfg.chain_costs : nullptr, SA_SUBSET_SPLIT, &oh, &n_oh, &sc, nullptr);
                     std::string sname = base + ".net.chains";
                     f = fopen((cfg.outdir + "/" + sname).c_str(), "w");
@@ -505,7 +555,17 @@ static void usage() {
             "  --gpu_net_subset (with --gpu_net: a .net.chains file next to each .net file: every fill's part of its chain as a chain of its\n"
             "      own, cut where a lower chain fills one of its gaps, clipped members rescored, under the penalties of --gpu_chain_all and\n"
             "      --gpu_chain_costs; per sub-chain a line `#chain k fill=F run=R score=S` with its target and query extents, then its members\n"
-            "      as .segments lines; with --gpu_stitch also a .net.maf file: those sub-chains stitched, in the .stitched.maf layout)\n");
+            "      as .segments lines; with --gpu_stitch also a .net.maf file: those sub-chains stitched, in the .stitched.maf layout)\n"
+            "  --gpu_net_class (with --gpu_net: a .net.class file next to each .net file: its lines with ' type=<top|syn|inv|nonSyn> qover=N\n"
+            "      qfar=N qdup=N' appended to every fill line: a fill without a parent is top; one on another query record than its parent is\n"
+            "      nonSyn; otherwise syn, with the bases its query extent shares with its parent's (qover) or the distance between the two\n"
+            "      (qfar); qdup counts its query bases that another fill of the file claims too.  A file holds one strand, so inv, a fill on\n"
+            "      the other strand than its parent, cannot occur here: it is reachable through sa_net_classify only)\n"
+            "  --gpu_net_syn=min_score,min_top_score,min_size,min_ali,max_far (implies --gpu_net_class: a fill is kept if it scores at least\n"
+            "      min_score, spans at least min_size target bases, holds at least min_ali aligned bases and, as a top fill, scores at least\n"
+            "      min_top_score, as a syn fill lies at most max_far from its parent on the query; a nonSyn fill is dropped, and a dropped\n"
+            "      fill takes the fills inside its gaps with it.  The .net.class file then holds the kept fills only, and --gpu_net_subset\n"
+            "      works on them: .net.chains and .net.maf are the syntenic net's alignments)\n");
 }
 
 // A gap-cost table in axtChain's linearGap layout (see usage).  The file's form is checked here; the values are checked again by the
@@ -649,6 +709,18 @@ int main(int argc, char** argv) {
             cfg.net_space = (uint32_t)ms;
         }
         else if (!strcmp(a, "--gpu_net_subset")) cfg.gpu_net_subset = true;
+        else if (!strcmp(a, "--gpu_net_class")) cfg.gpu_net_class = true;
+        else if (opt(a, "--gpu_net_syn", v)) {
+            long long t[5];
+            char tail = 0;
+            const bool ok = sscanf(v.c_str(), "%lld,%lld,%lld,%lld,%lld%c", &t[0], &t[1], &t[2], &t[3], &t[4], &tail) == 5;
+            if (!ok || t[2] < 0 || t[2] > (1ll << 31) || t[3] < 0 || t[3] > (1ll << 31) || t[4] < 0 || t[4] > (1ll << 31)) {
+                fprintf(stderr, "bad --gpu_net_syn=%s (min_score,min_top_score,min_size,min_ali,max_far; the last three 0 .. 2147483648)\n", v.c_str());
+                return 1;
+            }
+            cfg.net_syn_p = {t[0], t[1], (uint32_t)t[2], (uint32_t)t[3], (uint32_t)t[4], 0};
+            cfg.net_syn = cfg.gpu_net_class = true;
+        }
         else if (opt(a, "--gpu_net_fill", v)) {
             char* endp = nullptr;
             const long long mf = strtoll(v.c_str(), &endp, 10);
@@ -673,6 +745,7 @@ int main(int argc, char** argv) {
     if (cfg.stitch_min_set && !cfg.gpu_stitch) { fprintf(stderr, "--gpu_stitch_min needs --gpu_stitch\n"); return 1; }
     if (cfg.gpu_net && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_net needs --gpu_chain_all\n"); return 1; }
     if (cfg.gpu_net_subset && !cfg.gpu_net) { fprintf(stderr, "--gpu_net_subset needs --gpu_net and --gpu_chain_all\n"); return 1; }
+    if (cfg.gpu_net_class && !cfg.gpu_net) { fprintf(stderr, "%s needs --gpu_net and --gpu_chain_all\n", cfg.net_syn ? "--gpu_net_syn" : "--gpu_net_class"); return 1; }
     if (cfg.net_fill_set && !cfg.gpu_net) { fprintf(stderr, "--gpu_net_fill needs --gpu_net and --gpu_chain_all\n"); return 1; }
     cfg.target = pos[0];
     cfg.query = pos[1];

@@ -37,9 +37,15 @@ With --net-subset (which implies --net) the fills go through sa_net_subset with 
 line then adds fills, runs, members, cut members, bases rescored, the output bytes and subset ms beside net ms and peel ms.  Output HSPs
 and sub-chains are checked against the model (tests/net_subset_model.py) once per run.
 
+With --net-class [--net-class-filter S,T,Z,A,F] (which implies --net) the fills go through sa_net_classify with the query as the other
+axis, once without a filter and once under the given thresholds (min_score, min_top_score, min_size, min_ali, max_far):
+the line then adds the fills per class, clipped blocks, events, the sum of odup, the fills kept under the filter, the entry's own kernel
+launches (the sort's come on top) and class ms, the least of the repeats, beside net ms and, with --net-subset, subset ms.  The records
+and counts of both calls are checked against the model (tests/net_class_model.py) once per run.
+
   python tools/gapped_bench.py [--workloads standin,lumpy] [--repeat 3] [--align] [--greedy] [--batches 1024,2048,...]
                                [--pieces N] [--max-extent M] [--chain] [--chain-pen D,A] [--chain-costs T] [--chain-all] [--chain-min N] [--stitch] [--stitch-max-link N]
-                               [--net] [--net-space N] [--net-fill N] [--net-subset]
+                               [--net] [--net-space N] [--net-fill N] [--net-subset] [--net-class] [--net-class-filter S,T,Z,A,F]
 """
 import argparse
 import functools
@@ -237,9 +243,39 @@ def subset_fields(hsps, mem, first, fills, repeat, pen, net_ms, peel_ms):
             "subset_model_s": round(model_s, 1)}
 
 
+def class_fields(hsps, mem, first, bs, be, fills, repeat, thresholds, net_ms, subset_ms):
+    """sa_net_classify on the fills of the net with the query as the other axis (one query record, one strand), without a filter (the
+    run with the least class time) and under `thresholds`, both checked against the model."""
+    import net_class_model as NC
+    obs, obe = E.net_other_blocks(hsps, mem, first, axis="target")
+    flt = dict(zip(NC.THRESHOLDS, thresholds))
+    best = None
+    for _ in range(repeat):
+        t0 = time.perf_counter()
+        r = E.NetClassify(first, bs, be, obs, obe, fills)
+        wall = (time.perf_counter() - t0) * 1e3
+        if best is None or r[1]["class_ms"] < best[0][1]["class_ms"]:
+            best = (r, wall)
+    (cls, st), wall = best
+    fcls, fst = E.NetClassify(first, bs, be, obs, obe, fills, filter=flt)
+    t0 = time.perf_counter()
+    for got, got_st, want in ((cls, st, NC.classify(first, bs, be, obs, obe, fills)), (fcls, fst, NC.classify(first, bs, be, obs, obe, fills, filter=flt))):
+        if not np.array_equal(got, want[0].astype(got.dtype)) or any((list(got_st[k]) if k == "n_type" else got_st[k]) != want[1][k] for k in NC.COUNTS):
+            raise SystemExit("sa_net_classify differs from the model")
+    model_s = time.perf_counter() - t0
+    return {"class_fills": int(st["fills"]), **{"class_" + n: int(st["n_type"][k]) for k, n in enumerate(NC.NAMES)},
+            "class_blocks": int(st["blocks"]), "class_events": int(st["events"]), "class_dup_bases": int(st["dup_bases"]),
+            "class_filter": ",".join(str(int(x)) for x in thresholds), "class_kept": int(fst["kept"]),
+            "class_launches": 18, "class_launches_filtered": 19,  # counts, emit, flags, segments, block_dup, classes (keep); four scans of three
+            "class_ms": round(st["class_ms"], 3), "class_filtered_ms": round(fst["class_ms"], 3), "class_net_ms": round(net_ms, 3),
+            "class_subset_ms": None if subset_ms is None else round(subset_ms, 3), "class_call_ms": round(wall, 3),
+            "class_over_net": round(st["class_ms"] / net_ms, 4) if net_ms > 0 else None, "class_model_checked": True,
+            "class_model_s": round(model_s, 1)}
+
+
 def net_fields(hsps, chains, members, repeat, net, peel_ms, dp_ms, pen=(0, 0)):
     """sa_net_chains on the kept chains' target blocks, the run with the least net time, checked against the model; net[2]: also
-    subset_fields on its fills."""
+    subset_fields on its fills; net[3]: also class_fields on them, under the thresholds net[4]."""
     import net_model as N
     mem, first = E.chain_csr(members)
     bs, be = E.net_blocks(hsps, mem, first, axis="target")
@@ -257,6 +293,8 @@ def net_fields(hsps, chains, members, repeat, net, peel_ms, dp_ms, pen=(0, 0)):
     if not np.array_equal(fills, want.astype(fills.dtype)) or any(st[k] != want_st[k] for k in ("fills", "filled", "max_depth")):
         raise SystemExit("sa_net_chains differs from the model")
     extra = subset_fields(hsps, mem, first, fills, repeat, pen, st["net_ms"], peel_ms) if len(net) > 2 and net[2] else {}
+    if len(net) > 3 and net[3]:
+        extra.update(class_fields(hsps, mem, first, bs, be, fills, repeat, net[4], st["net_ms"], extra.get("subset_ms")))
     return {**extra, "net_min_space": int(net[0]), "net_min_fill": int(net[1]), "net_chains": int(st["chains"]), "net_blocks": int(st["blocks"]),
             "net_fills": int(st["fills"]), "net_rounds": int(st["rounds"]), "net_spaces": int(st["spaces"]), "net_max_depth": int(st["max_depth"]),
             "net_chains_without_fill": int(st["chains"] - st["filled"]), "net_prep_ms": round(st["prep_ms"], 3), "net_ms": round(st["net_ms"], 3),
@@ -436,8 +474,14 @@ def main():
     ap.add_argument("--net-space", type=int, default=1, help="with --net: min_space")
     ap.add_argument("--net-fill", type=int, default=1, help="with --net: min_fill")
     ap.add_argument("--net-subset", action="store_true", help="also cut the fills into sub-chains (sa_net_subset); implies --net")
+    ap.add_argument("--net-class", action="store_true", help="also class the fills against their parents on the query (sa_net_classify); implies --net")
+    ap.add_argument("--net-class-filter", default="3000,5000,30,25,100000",
+                    help="with --net-class: min_score,min_top_score,min_size,min_ali,max_far of the filtered call")
     a = ap.parse_args()
-    a.net = a.net or a.net_subset
+    a.net = a.net or a.net_subset or a.net_class
+    class_filter = tuple(int(x) for x in a.net_class_filter.split(","))
+    if len(class_filter) != 5:
+        ap.error("--net-class-filter takes five values")
     a.chain_all = a.chain_all or a.stitch or a.net
     chain = tuple(int(x) for x in a.chain_pen.split(",")) if a.chain or a.chain_all else None
     if a.chain_costs and chain is None:
@@ -447,7 +491,7 @@ def main():
     for name in a.workloads.split(","):
         if not a.batches:
             print(json.dumps(run(name, a.repeat, a.align, a.greedy, pieces=a.pieces, chain=chain, chain_all_min=a.chain_min if a.chain_all else None,
-                                 stitch=a.stitch_max_link if a.stitch else None, net=(a.net_space, a.net_fill, a.net_subset) if a.net else None,
+                                 stitch=a.stitch_max_link if a.stitch else None, net=(a.net_space, a.net_fill, a.net_subset, a.net_class, class_filter) if a.net else None,
                                  chain_costs=a.chain_costs or None)), flush=True)
             continue
         for b in a.batches.split(","):
