@@ -1,6 +1,6 @@
 // api_hspchain.hip -- C-ABI sa_chain_hsps: the best collinear chain of every group of HSPs (contract: include/segalign_amd.h),
 // and sa_chain_hsps_all: all chains of every group, peeled best first; sa_chain_hsps_costs and sa_chain_hsps_all_costs:
-// the two under a piecewise-linear gap-cost table, which only picks another pair of DP kernels (hspcost.hip).
+// the two under a piecewise-linear gap-cost table, which only hands the DP's launches the table's device image.
 // The host side: checks, the slot, rank (two stable radix sorts) and the tile loop (hspchain.hip: cross, resolve), shared by both; then
 // sa_chain_hsps's finish (group starts, ends, members, nodes) or the peel (hsppeel.hip: subtree minimum, chain order, members), and the
 // counts the kernels' work is reported by.
@@ -47,7 +47,7 @@ void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, u
     hipStream_t s = sl->stream;
 
     sa_segment_pair* d_hsps;
-    uint32_t *d_group, *idx_a, *rs, *qs, *ln, *gr, *pred, *first;
+    uint32_t *d_group, *idx_a, *rs, *qs, *ln, *gr, *pred, *first, *d_image;
     int32_t* sc;
     int64_t* f;
     carve(sl->hspchain_work, "hsp chain", [&](Carve& c) {
@@ -55,7 +55,7 @@ void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, u
         c.take(rs, N).take(qs, N).take(ln, N).take(gr, N).take(sc, N).take(f, N).take(pred, N);
         c.take(d.head, (size_t)N + 1).take(d.gidx, (size_t)N + 1).take(first, tiles);
         c.take(d.gstart, N).take(d.gend, N).take(d.glen, (size_t)N + 1).take(d.goff, (size_t)N + 1);
-        c.take(d.d_members, N).take(d.d_nodes, N);
+        c.take(d.d_members, N).take(d.d_nodes, N).take(d_image, HSPCOST_WORDS);
     });
     if (!group) d_group = nullptr;
     sl->hspchain_partial.ensure((size_t)tiles * T * sizeof(HspChainPartial), "hsp chain partials");
@@ -66,7 +66,6 @@ void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, u
     d.temp_bytes = std::max(sort_bytes, scan_bytes);
     sl->hspchain_temp.ensure(std::max<size_t>(d.temp_bytes, 256), "hsp chain temp");
     void* temp = d.temp = sl->hspchain_temp.p;
-    if (costs.on) sl->hspcost_image.ensure(sizeof(costs.w), "hsp chain gap costs");
 
     HspChainArgs& a = d.a;
     a.rs = rs; a.qs = qs; a.ln = ln; a.gr = gr; a.sc = sc; a.f = f; a.pred = pred;
@@ -75,13 +74,11 @@ void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, u
     a.diag_pen = d.P.diag_pen;
     a.anti_pen = d.P.anti_pen;
     a.max_gap = d.P.max_gap;
-    HspCostArgs ca;
-    ca.c = a;
-    ca.image = costs.on ? (const uint32_t*)sl->hspcost_image.p : nullptr;
+    const uint32_t* image = costs.on ? d_image : nullptr;  // picks the DP's instances, and the scope names they are profiled under
 
     check_memcpy(hipMemcpyAsync(d_hsps, hsps, n * sizeof(sa_segment_pair), hipMemcpyHostToDevice, s), "hsp chain: HSPs");
     if (group) check_memcpy(hipMemcpyAsync(d_group, group, n * sizeof(uint32_t), hipMemcpyHostToDevice, s), "hsp chain: groups");
-    if (costs.on) check_memcpy(hipMemcpyAsync(sl->hspcost_image.p, costs.w, sizeof(costs.w), hipMemcpyHostToDevice, s), "hsp chain: gap costs");
+    if (costs.on) check_memcpy(hipMemcpyAsync(d_image, costs.w, sizeof(costs.w), hipMemcpyHostToDevice, s), "hsp chain: gap costs");
 
     // rank: stable sort by (query_start, len) with the input index as value, then by (group, ref_start); idx_a ends up as rank -> input index
     std::vector<uint32_t> h_first(tiles);
@@ -108,14 +105,12 @@ void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, u
             exit(15);
         }
         if (b > c0) {
-            ProfScope ps(sl, costs.on ? "hspcost_cross" : "hspchain_cross");
-            if (costs.on) launch_hspcost_cross(ca, b, c0, partial, s);
-            else launch_hspchain_cross(a, b, c0, partial, s);
+            ProfScope ps(sl, image ? "hspcost_cross" : "hspchain_cross");
+            launch_hspchain_cross(a, b, c0, partial, image, s);
         }
         {
-            ProfScope ps(sl, costs.on ? "hspcost_resolve" : "hspchain_resolve");
-            if (costs.on) launch_hspcost_resolve(ca, b, c0, partial, s);
-            else launch_hspchain_resolve(a, b, c0, partial, s);
+            ProfScope ps(sl, image ? "hspcost_resolve" : "hspchain_resolve");
+            launch_hspchain_resolve(a, b, c0, partial, image, s);
         }
         check_launch("hspchain tile");
         st.pair_evals += (uint64_t)(b - c0) * T * nb + (uint64_t)nb * (nb - 1) / 2;

@@ -20,8 +20,8 @@
 //   post_host.h        what those six share on the host: event timing, checked launches, buffer carving, caller-owned arrays, trace batches
 //   gapped.hip         kernels of the gapped entries: y-drop extension of a side, trace sweep, path walk (gapped.h)
 //   cover.hip          kernels and rocPRIM steps of the greedy cover index; its sort and scan wrappers also serve api_hspchain.hip (gapped.h)
-//   hspchain.hip       kernels of the chaining DP: rank keys, gather, tile cross / resolve, group ends, members, nodes (hspchain.h)
-//   hspcost.hip        the cross / resolve kernels of the chaining DP under a piecewise-linear gap-cost table (hspcost.h)
+//   hspchain.hip       kernels of the chaining DP: rank keys, gather, tile cross / resolve with or without a gap-cost table, group ends,
+//                      members, nodes (hspchain.h; the table's image and lookup: hspcost.h)
 //   hsppeel.hip        kernels of the peel into all chains: subtree minimum, chain order, members, records (hsppeel.h)
 //   stitch.hip         kernels of the stitch: member scores, the global sweep of a link in five instances (stitch.h)
 //   net.hip            kernels of the net: priority order, hulls, and a round's search, count and emit, one wavefront per space (net.h)
@@ -351,11 +351,10 @@ struct Slot {
     DevBuf<uint64_t> cover_key[2], cover_run[2];
     DevBuf<uint8_t> cover_segs, cover_work, cover_temp;
     DevBuf<uint32_t> cover_edges;
-    // sa_chain_hsps (api_hspchain.hip, hspchain.hip): the ranked HSPs with f and pred, sort keys and finish arrays, the cross launches'
-    // partial bests, rocPRIM's temporary storage
+    // sa_chain_hsps (api_hspchain.hip, hspchain.hip): the ranked HSPs with f and pred, sort keys, finish arrays and the image of a
+    // gap-cost table (hspcost.h); the cross launches' partial bests; rocPRIM's temporary storage
     DevBuf<uint8_t> hspchain_work, hspchain_partial, hspchain_temp;
     DevBuf<uint8_t> hsppeel_work;     // sa_chain_hsps_all (api_hspchain.hip, hsppeel.hip): everything the peel adds to the above
-    DevBuf<uint8_t> hspcost_image;    // sa_chain_hsps_costs, sa_chain_hsps_all_costs (hspcost.hip): the gap-cost table with its slopes (hspcost.h)
     DevBuf<uint8_t> stitch;           // sa_stitch_chains (api_stitch.hip, stitch.hip): the members and their scores, then a batch's link tasks,
                                       // scores, walk results, op areas and trace areas
     // sa_net_chains (api_net.hip, net.hip): the input and what the prepare step makes of it; a round's hits, counts and offsets, then the

@@ -38,10 +38,12 @@ void launch_hspchain_gather(const sa_segment_pair* hsps, const uint32_t* group, 
 void launch_hspchain_first(const uint32_t* gr, uint32_t n, uint32_t tile, uint32_t* first, hipStream_t s);
 
 // ---- the DP, tile by tile in rank order ----
+// image: the device image of a gap-cost table (hspcost.h: HSPCOST_WORDS words, 16-byte aligned), whose cost joins the penalty of every
+// link, or nullptr for the linear penalty alone; same grid and same partials either way.
 // Cross: workgroup k of b - c0 offers tile c = c0 + k to every node of tile b; partial[k * tile + t] for node b * tile + t.
-void launch_hspchain_cross(const HspChainArgs& a, uint32_t b, uint32_t c0, HspChainPartial* partial, hipStream_t s);
+void launch_hspchain_cross(const HspChainArgs& a, uint32_t b, uint32_t c0, HspChainPartial* partial, const uint32_t* image, hipStream_t s);
 // Resolve: one workgroup reduces tile b's partials over c, settles the tile's own dependencies and writes its f and pred.
-void launch_hspchain_resolve(const HspChainArgs& a, uint32_t b, uint32_t c0, const HspChainPartial* partial, hipStream_t s);
+void launch_hspchain_resolve(const HspChainArgs& a, uint32_t b, uint32_t c0, const HspChainPartial* partial, const uint32_t* image, hipStream_t s);
 
 // ---- finish ----
 // gstart[g] = first rank of the g-th group, from the head flags and their exclusive scan.

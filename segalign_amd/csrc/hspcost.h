@@ -1,7 +1,10 @@
-// hspcost.h -- what hspcost.hip (the DP kernels under a gap-cost table) and api_hspchain.hip (sa_chain_hsps_costs, sa_chain_hsps_all_costs)
-// share.  Contract: include/segalign_amd.h, DESIGN.md 20.
+// hspcost.h -- the device image of a gap-cost table and its lookup: what hspchain.hip (the DP's <true> instances), netsubset.hip and
+// post_host.h (which builds the image) share.  Contract: include/segalign_amd.h, DESIGN.md 20.
 #pragma once
-#include "hspchain.h"
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/segalign_amd.h"
 
 namespace sa {
 
@@ -14,7 +17,7 @@ constexpr uint32_t HSPCOST_ROW0 = HSPCOST_POINTS;                       // first
 constexpr uint32_t HSPCOST_WORDS = HSPCOST_POINTS + 3 * HSPCOST_POINTS * 4;  // 208 words, 832 bytes
 constexpr uint32_t HSPCOST_SLOPE_LIMIT = 1u << 27;
 
-// The gap cost of a link with gaps dt, dq from an image, in LDS (hspcost.hip) or in global memory (netsubset.hip): the one lookup both
+// The gap cost of a link with gaps dt, dq from an image, in LDS (hspchain.hip) or in global memory (netsubset.hip): the one lookup both
 // units use, so that a sub-chain is priced as its chain was.  For a pair that is no link (a negative gap) the value is arbitrary but
 // every step stays in range: the search clamps x into 32 bits, the distance past the break point is clamped at 0.
 __device__ __forceinline__ int64_t hspcost_gapcost(const uint32_t* img, int64_t dt, int64_t dq) {
@@ -34,14 +37,5 @@ __device__ __forceinline__ int64_t hspcost_gapcost(const uint32_t* img, int64_t 
     const int64_t g = (int64_t)((uint64_t)row.x | (uint64_t)row.y << 32) + (int64_t)(prod >> 16);
     return x == 0 ? 0 : g;
 }
-
-struct HspCostArgs {
-    HspChainArgs c;         // the ranked HSPs, f and pred, the tile and the linear terms: as the linear kernels take them
-    const uint32_t* image;  // HSPCOST_WORDS words, 16-byte aligned
-};
-
-// The cross and resolve steps of hspchain.h with the gap cost added to the penalty; same grid, same partials.
-void launch_hspcost_cross(const HspCostArgs& a, uint32_t b, uint32_t c0, HspChainPartial* partial, hipStream_t s);
-void launch_hspcost_resolve(const HspCostArgs& a, uint32_t b, uint32_t c0, const HspChainPartial* partial, hipStream_t s);
 
 }  // namespace sa

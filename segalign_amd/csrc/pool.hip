@@ -131,7 +131,6 @@ void slot_destroy(Slot& s) {
     s.hspchain_partial.release("hsp chain partials");
     s.hspchain_temp.release("hsp chain temp");
     s.hsppeel_work.release("hsp peel");
-    s.hspcost_image.release("hsp chain gap costs");
     s.stitch.release("stitch");
     s.net_work.release("net");
     s.net_round.release("net round");

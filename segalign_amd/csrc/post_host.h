@@ -102,7 +102,7 @@ void resident_block(const char* who, const Slot* sl, int rev, uint32_t buffer, A
     a.sub_mat = dc->d_sub_mat;
 }
 
-// A gap-cost table as the kernels of hspcost.hip and netsubset.hip read it (layout: hspcost.h), or none.
+// A gap-cost table as the kernels of hspchain.hip and netsubset.hip read it (layout: hspcost.h), or none.
 struct CostImage {
     bool on = false;
     uint32_t w[HSPCOST_WORDS];

@@ -1,8 +1,9 @@
 """CPU: the chaining kernels (segalign_amd/csrc/hspchain.hip) as the compiler reports them: every kernel is there and none
-spills to scratch memory."""
+spills to scratch memory.  The two DP kernels are templates on whether a gap-cost table is in force: both instances count."""
 from segalign_amd.build import kernel_resources
 
-KERNELS = ["hspchain_cross_kernel", "hspchain_resolve_kernel", "hspchain_key_minor_kernel", "hspchain_key_major_kernel",
+KERNELS = ["hspchain_cross_kernel<false>", "hspchain_cross_kernel<true>", "hspchain_resolve_kernel<false>", "hspchain_resolve_kernel<true>",
+           "hspchain_key_minor_kernel", "hspchain_key_major_kernel",
            "hspchain_gather_kernel", "hspchain_first_kernel", "hspchain_group_starts_kernel", "hspchain_ends_kernel",
            "hspchain_members_kernel", "hspchain_nodes_kernel"]
 
