@@ -335,6 +335,45 @@ int sa_copy_neighbourhood_starts(int dev, uint64_t first_key, uint64_t count, ui
  * uint32 seed start positions in mode 1.  Returns which (2 or 1), or -1 with a message as above. */
 int sa_copy_neighbourhood_records(int dev, uint64_t first_entry, uint64_t count, void* dst);
 
+/* Test entries (read-only; tests/test_gpu_sequence_images.py, DESIGN.md 4.1'): the images of the resident blocks of device `dev` as
+ * their builders (encode.hip, SeqBuf / PackedBuf) left them -- the WHOLE span a builder defines, guards, pads and zero tails included,
+ * not just the bases.  `buffer` is the query buffer of SA_IMAGE_QUERY* and ignored otherwise.
+ *   sequence buffers (REF, REF8, REF_RC, QUERY, QUERY_RC): len + 2 * 64 + 64 bytes, one copy, byte 0 (base 0) at `origin` = 64;
+ *   4-bit copies (QUERY4, QUERY4_RC, REF4, REF4_RC): 8 copies of `stride` bytes, byte 0 of copy c at c * stride + `origin` (64);
+ *   REF2: the 4 overlapped-line phase copies, `stride` = the physical bytes of one, origin 0;
+ *   2-bit shifted copies (QUERY2, QUERY2_RC, REFQ2, REFQ2_RC): `copies` (1, or 16 under option cls_one_copy = 2) of `stride` bytes, origin 0.
+ * sa_copy_image fills *info, and with dst != NULL and cap >= info->bytes copies the span.  0; -1 with a message on stderr and nothing
+ * copied when the image is missing (not sent, cleared, the repeat masker's copies before sa_rm_send_query_write_request), the
+ * arguments are out of range or cap is too small (*info is filled then if the image exists). */
+#define SA_IMAGE_REF 0
+#define SA_IMAGE_REF8 1
+#define SA_IMAGE_REF_RC 2
+#define SA_IMAGE_QUERY 3
+#define SA_IMAGE_QUERY_RC 4
+#define SA_IMAGE_QUERY4 5
+#define SA_IMAGE_QUERY4_RC 6
+#define SA_IMAGE_REF4 7
+#define SA_IMAGE_REF4_RC 8
+#define SA_IMAGE_REF2 9
+#define SA_IMAGE_QUERY2 10
+#define SA_IMAGE_QUERY2_RC 11
+#define SA_IMAGE_REFQ2 12
+#define SA_IMAGE_REFQ2_RC 13
+#define SA_IMAGE_COUNT 14
+typedef struct sa_image_info {
+    uint64_t bytes;              /* the span: copies * stride (sequence buffers: len + 192) */
+    uint64_t stride;             /* bytes from one copy to the next (sequence buffers: == bytes) */
+    uint64_t origin;             /* offset of byte 0 of copy 0 inside the span */
+    uint32_t len;                /* bases of the block the image belongs to */
+    uint32_t copies;
+} sa_image_info;
+int sa_copy_image(int dev, int image, uint32_t buffer, uint8_t* dst, uint64_t cap, sa_image_info* info);
+/* the code-presence masks the host holds for device `dev` (bit c: code c occurs in the block; 0xFF before a block was sent):
+ * *ref_present, query_present[SA_BUFFER_DEPTH].  0, or -1 with a message */
+int sa_get_code_presence(int dev, uint32_t* ref_present, uint32_t* query_present);
+/* the class filter's four class scores for these two masks under the resident matrix (sa_initialize_processor).  0, or -1 */
+int sa_get_class_scores(uint32_t present_t, uint32_t present_q, int32_t* cls4);
+
 /* Test entry (read-only; tests/test_gpu_probe_regimes.py, DESIGN.md 4.4'): the FRONT of a table-direct call alone -- position probe,
  * workgroup sums, compaction, head bits, chunk plans -- and everything it wrote.  [start, end) of strand `rev` of query `buffer` on
  * the resident target is clipped to the positions whose seed window lies inside the query and cut into sa_get_wga_chunk()-sized

@@ -116,6 +116,95 @@ int sa_copy_neighbourhood_records(int dev, uint64_t first_entry, uint64_t count,
     return 1;
 }
 
+// ---- the sequence images as their builders left them (tests/test_gpu_sequence_images.py, DESIGN.md 4.1') ----------------------------------
+// Whole spans: a sequence buffer with its guards and over-read room, the 4-bit copies with their pads, the overlapped lines of the
+// target's 2-bit copies, the shifted 2-bit copies with their zero tails.  Read-only; the send entries have synchronised their stream.
+static_assert(SA_IMAGE_COUNT == 14 && SA_IMAGE_REFQ2_RC == SA_IMAGE_COUNT - 1, "sa_copy_image knows every image");
+static_assert(sizeof(sa_image_info) == 32 && offsetof(sa_image_info, len) == 24, "sa_image_info as engine.py restates it");
+int sa_copy_image(int dev, int image, uint32_t buffer, uint8_t* dst, uint64_t cap, sa_image_info* o) {
+    memset(o, 0, sizeof(*o));
+    if (dev < 0 || dev >= g_ndev || image < 0 || image >= SA_IMAGE_COUNT) {
+        fprintf(stderr, "Error: sa_copy_image: device %d or image %d out of range\n", dev, image);
+        return -1;
+    }
+    const bool of_query = image == SA_IMAGE_QUERY || image == SA_IMAGE_QUERY_RC || image == SA_IMAGE_QUERY4 || image == SA_IMAGE_QUERY4_RC ||
+                          image == SA_IMAGE_QUERY2 || image == SA_IMAGE_QUERY2_RC;
+    if (of_query && buffer >= SA_BUFFER_DEPTH) {
+        fprintf(stderr, "Error: sa_copy_image: query buffer %u out of range\n", buffer);
+        return -1;
+    }
+    DevCtx* dc = g_dev[dev];
+    const uint32_t b = of_query ? buffer : 0;
+    const SeqBuf* sb = nullptr;
+    const PackedBuf* pb = nullptr;
+    switch (image) {
+        case SA_IMAGE_REF: sb = &dc->ref; break;
+        case SA_IMAGE_REF8: sb = &dc->ref8; break;
+        case SA_IMAGE_REF_RC: sb = &dc->ref_rc; break;
+        case SA_IMAGE_QUERY: sb = &dc->query[b]; break;
+        case SA_IMAGE_QUERY_RC: sb = &dc->query_rc[b]; break;
+        case SA_IMAGE_QUERY4: pb = &dc->query4[b]; break;
+        case SA_IMAGE_QUERY4_RC: pb = &dc->query4_rc[b]; break;
+        case SA_IMAGE_REF4: pb = &dc->ref4; break;
+        case SA_IMAGE_REF4_RC: pb = &dc->ref4_rc; break;
+        case SA_IMAGE_REF2: pb = &dc->ref2; break;
+        case SA_IMAGE_QUERY2: pb = &dc->query2[b]; break;
+        case SA_IMAGE_QUERY2_RC: pb = &dc->query2_rc[b]; break;
+        case SA_IMAGE_REFQ2: pb = &dc->refq2; break;
+        default: pb = &dc->refq2_rc; break;
+    }
+    const uint8_t* src = nullptr;
+    if (sb) {
+        if (sb->alloc && sb->codes) {
+            src = sb->alloc;
+            o->bytes = o->stride = (uint64_t)sb->len + 2 * SEQ_PAD + 64;
+            o->origin = SEQ_PAD;
+            o->len = sb->len;
+            o->copies = 1;
+        }
+    } else if (pb->alloc && pb->base && pb->stride) {
+        const bool four = image == SA_IMAGE_QUERY4 || image == SA_IMAGE_QUERY4_RC || image == SA_IMAGE_REF4 || image == SA_IMAGE_REF4_RC;
+        src = pb->alloc;
+        o->stride = pb->stride;
+        o->copies = four ? (uint32_t)PACK4_COPIES : image == SA_IMAGE_REF2 ? 4u : pb->copies;
+        o->origin = (uint64_t)(pb->base - pb->alloc);
+        o->bytes = o->stride * o->copies;
+        o->len = of_query ? g_query_len[b] : dc->ref.len;
+    }
+    if (!src || o->bytes > (uint64_t)(sb ? sb->cap : pb->cap)) {
+        fprintf(stderr, "Error: sa_copy_image: image %d of device %d is not resident\n", image, dev);
+        memset(o, 0, sizeof(*o));
+        return -1;
+    }
+    if (!dst) return 0;
+    if (cap < o->bytes) {
+        fprintf(stderr, "Error: sa_copy_image: image %d spans %llu bytes, room for %llu\n", image, (unsigned long long)o->bytes, (unsigned long long)cap);
+        return -1;
+    }
+    check_set_device(dc->dev, "copy");
+    check_memcpy(hipMemcpy(dst, src, o->bytes, hipMemcpyDeviceToHost), "image");
+    return 0;
+}
+int sa_get_code_presence(int dev, uint32_t* ref_present, uint32_t* query_present) {
+    if (dev < 0 || dev >= g_ndev) {
+        fprintf(stderr, "Error: sa_get_code_presence: device %d out of range\n", dev);
+        return -1;
+    }
+    *ref_present = g_dev[dev]->ref_present;
+    for (int b = 0; b < SA_BUFFER_DEPTH; b++) query_present[b] = g_dev[dev]->query_present[b];
+    return 0;
+}
+int sa_get_class_scores(uint32_t present_t, uint32_t present_q, int32_t* cls4) {
+    if (!g_proc_init) {
+        fprintf(stderr, "Error: sa_get_class_scores before InitializeProcessor: no matrix is resident\n");
+        return -1;
+    }
+    int cls[4];
+    class_scores(present_t, present_q, cls);
+    for (int x = 0; x < 4; x++) cls4[x] = cls[x];
+    return 0;
+}
+
 // ---- the front of a table-direct call alone (tests/test_gpu_probe_regimes.py, DESIGN.md 4.4') -------------------------------------------
 // The range is clipped and cut into chunks as chunks_pass (api_calls.hip) does it, a slot is taken as calls take one, the unchanged
 // td_front runs, and what it left in the slot is copied out.  Nothing of a call's later stages runs; t_stats is left alone.

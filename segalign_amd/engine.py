@@ -40,6 +40,7 @@ C_ABI_SYMBOLS = [
     "sa_get_lookup_mode", "sa_get_neighbourhood_entries",
     "sa_get_table_build_info", "sa_copy_neighbourhood_starts", "sa_copy_neighbourhood_records",
     "sa_probe_call", "sa_free_probe_call",
+    "sa_copy_image", "sa_get_code_presence", "sa_get_class_scores",
     "sa_seed_calls", "sa_count_call_hits", "sa_count_chunk_hits", "sa_get_wga_chunk", "sa_release_arena", "sa_set_option", "sa_reset_option", "sa_get_option", "sa_option_count", "sa_option_name", "sa_get_audit",
     "sa_gapped_extend", "sa_free_gapped", "sa_gapped_align", "sa_free_gapped_align", "sa_gapped_align_greedy",
     "sa_chain_hsps", "sa_free_chain", "sa_chain_hsps_all", "sa_free_chain_all",
@@ -203,6 +204,15 @@ class ProbeResult(C.Structure):  # sa_probe_result
                 ("head_bits", C.c_void_p), ("td_chunk", C.c_void_p), ("seg_end", C.c_void_p), ("t_off", C.c_void_p), ("t_cnt", C.c_void_p)]
 
 
+# sa_copy_image (test entry, DESIGN.md 4.1'): the images the send entries build from a block, whole spans
+IMAGES = ("ref", "ref8", "ref_rc", "query", "query_rc", "query4", "query4_rc", "ref4", "ref4_rc", "ref2", "query2", "query2_rc", "refq2",
+          "refq2_rc")  # SA_IMAGE_*: the index is the id
+
+
+class ImageInfo(C.Structure):  # sa_image_info
+    _fields_ = [("bytes", C.c_uint64), ("stride", C.c_uint64), ("origin", C.c_uint64), ("len", C.c_uint32), ("copies", C.c_uint32)]
+
+
 TABLE_BUILD_NONE, TABLE_BUILD_TWO_LEVEL, TABLE_BUILD_THREE_LEVEL, TABLE_BUILD_ATOMIC, TABLE_BUILD_ATOMIC_GAVE_UP = 0, 1, 2, 3, 4
 NBR_FILL_NONE, NBR_FILL_ALIAS, NBR_FILL_POSITIONS, NBR_FILL_CTX_ONE_STAGE, NBR_FILL_CTX_DENSE, NBR_FILL_CTX_SPARSE = 0, 1, 2, 3, 4, 5
 CTX_DTYPE = np.dtype([("pos", "<u4"), ("w", "<u4", (7,))])  # CtxRec: a neighbourhood entry with its target context
@@ -287,6 +297,12 @@ def lib():
     L.sa_probe_call.restype = C.c_int
     L.sa_probe_call.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.POINTER(ProbeResult)]
     L.sa_free_probe_call.argtypes = [C.POINTER(ProbeResult)]
+    L.sa_copy_image.restype = C.c_int
+    L.sa_copy_image.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(ImageInfo)]
+    L.sa_get_code_presence.restype = C.c_int
+    L.sa_get_code_presence.argtypes = [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.sa_get_class_scores.restype = C.c_int
+    L.sa_get_class_scores.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]
     L.sa_version.restype = C.c_char_p
     L.sa_seed_calls.restype = C.c_size_t
     L.sa_seed_calls.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_void_p, C.POINTER(CallStats)]
@@ -1036,6 +1052,36 @@ def ProbeCall(start, end, rev=False, buffer=0, rm=False):
         return out
     finally:
         lib().sa_free_probe_call(C.byref(r))
+
+
+def copy_image(name, buffer=0, dev=0):
+    """The whole span of one image of the resident blocks (sa_copy_image; test entry; `name` in IMAGES) -> (info, bytes): info = {"bytes",
+    "stride", "origin", "len", "copies"}, bytes a uint8 array of the span.  None when the image is not resident."""
+    info = ImageInfo()
+    image = IMAGES.index(name)
+    if lib().sa_copy_image(dev, image, int(buffer), None, 0, C.byref(info)) != 0:
+        return None
+    out = np.empty(int(info.bytes), dtype=np.uint8)
+    if lib().sa_copy_image(dev, image, int(buffer), out.ctypes.data, out.size, C.byref(info)) != 0:
+        raise RuntimeError("sa_copy_image failed")
+    return {k: int(getattr(info, k)) for k, _ in ImageInfo._fields_}, out
+
+
+def code_presence(dev=0):
+    """(ref_present, [query_present of every buffer]): the masks the host holds (sa_get_code_presence; test entry)."""
+    r = C.c_uint32()
+    q = (C.c_uint32 * 2)()
+    if lib().sa_get_code_presence(dev, C.byref(r), q) != 0:
+        raise RuntimeError("sa_get_code_presence: device out of range")
+    return int(r.value), [int(v) for v in q]
+
+
+def class_scores(present_t, present_q):
+    """The class filter's class scores for two presence masks under the resident matrix (sa_get_class_scores; test entry)."""
+    cls = (C.c_int32 * 4)()
+    if lib().sa_get_class_scores(int(present_t), int(present_q), cls) != 0:
+        raise RuntimeError("sa_get_class_scores before InitializeProcessor")
+    return [int(v) for v in cls]
 
 
 def filter_mode():

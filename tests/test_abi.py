@@ -51,6 +51,23 @@ def test_probe_entry_structs_have_the_headers_layout():
         assert re.search(r"#define %s %d\b" % (name, value), hdr), name
 
 
+def test_image_entry_struct_and_ids_have_the_headers_layout():
+    """sa_copy_image fills one sa_image_info; its images are numbered by SA_IMAGE_*: engine.py's ImageInfo has the header's fields in the
+    header's order and size, and engine.IMAGES names the ids in their order (the library asserts size and count against its own)"""
+    import ctypes as C
+    from segalign_amd import engine as E
+    assert C.sizeof(E.ImageInfo) == 3 * 8 + 2 * 4 == 32
+    hdr = open(os.path.join(ROOT, "include", "segalign_amd.h")).read()
+    body = hdr[hdr.index("typedef struct sa_image_info {"):hdr.index("} sa_image_info;")]
+    decls = re.findall(r"^\s+(uint\d+_t)\s+(\w+);", body, flags=re.M)
+    assert [n for _, n in decls] == [n for n, _ in E.ImageInfo._fields_]
+    assert [getattr(C, "c_" + t[:-2]) for t, _ in decls] == [t for _, t in E.ImageInfo._fields_]
+    ids = dict(re.findall(r"#define SA_IMAGE_(\w+) (\d+)\b", hdr))
+    assert int(ids.pop("COUNT")) == len(E.IMAGES) == len(ids)
+    assert [k.lower() for k, _ in sorted(ids.items(), key=lambda kv: int(kv[1]))] == list(E.IMAGES)
+    assert sorted(int(v) for v in ids.values()) == list(range(len(E.IMAGES)))
+
+
 def test_product_never_touches_the_oracle():
     """The product path must not import, link or execute anything under oracle/ (no CPU fallback)."""
     pkg = os.path.join(ROOT, "segalign_amd")
