@@ -253,6 +253,15 @@ int sa_max_hits_for_mem(uint64_t total_global_mem);
  *   LDS-staged partition build is the default), work_gb (GiB of work arena per slot), arena_vmm, call_hits, call_hits_max
  * Test-only options (small capacities that force the overflow / fallback branches of the orchestration)
  *   l2_cap, spec_dedup, spec_recs, dedup_seg_max, no_small_dedup, chain_cap, chain_no_link, q2_limit_mb, audit_cap
+ *   cand_cap          records the candidate list of a batch is first sized for, in place of max(2^16, hits of the batch / 16)
+ *   ent_cap           the same for the list of hits that need the entropy factor, in place of max(2^16, hits of the batch / 32)
+ *   out_cap           the same for the survivor list of the call, in place of max(2^20, min(hits of the call, 2^26)); the kernels are
+ *                     given this capacity, the allocation keeps 131 072 records behind it (what the speculative chain may read)
+ *                     (each of the three: 0 = the sizing named; a list that overflows is regrown from the counts of the attempt and the
+ *                     batch runs again, SA_PATH_LIST_REGROWN.  Buffers only grow until sa_shutdown_processor, so a small value
+ *                     overflows only on a freshly initialised processor; sa_get_last_call_trace tells whether it did)
+ *   hit_batch         hits one extension batch of the general path may hold before the next reference iteration opens a new batch, in
+ *                     place of 2^27 (0 = 2^27); a single iteration is never cut
  */
 int sa_set_option(const char* name, int64_t value);
 int sa_reset_option(const char* name);     /* NULL: every option back to environment / default */
@@ -295,6 +304,36 @@ typedef struct sa_call_stats {
 /* bit 64u is retired (it was SA_PATH_KEY_ORDERED): never set, and no other flag takes its place */
 #define SA_PATH_GENERAL_FALLBACK 32u     /* a device-seeded call could not take the table-direct path (a chunk of 6 x MAX_HITS hits or more, > 2^32 hits, ...) */
 void sa_get_last_call_stats(sa_call_stats* out); /* stats of the calling thread's most recent hot call */
+
+/* Which way the calling thread's most recent hot call went through the call core (saf_core: batches, reruns, chain slices, output
+ * route).  Read-only, for tests: results never depend on it.  An entry that makes several calls (a pass that halves itself, the
+ * interval entries) leaves the trace of its last one. */
+typedef struct sa_call_trace {
+    uint32_t segments;          /* reference iterations of the call, over all its chunks */
+    uint32_t batches;           /* extension batches that ran (batches without hits are not counted) */
+    uint32_t reruns;            /* attempts of a batch beyond its first, summed over the batches */
+    int32_t rerun_first_batch;  /* first / last batch that ran more than once, counted among the batches that ran; -1: none */
+    int32_t rerun_last_batch;
+    uint32_t overflowed;        /* OR over the attempts that were repeated: SA_TRACE_OVER_* */
+    uint32_t slices;            /* chain slices run (SA_PATH_CHAIN_SLICED) */
+    uint32_t spec_tried;        /* the speculative per-segment LDS chain was launched on the device's survivor count */
+    uint32_t spec_refused;      /* ... and (last attempt) the device refused it: a segment or the call held too many records */
+    uint32_t second_copy;       /* records of the speculative chain fetched in a second copy (those beyond option spec_recs) */
+    uint32_t route;             /* SA_ROUTE_*: how the survivors reached the host */
+    uint32_t l2_max;            /* context-table calls: largest count of a second-level sub-list in any attempt */
+} sa_call_trace;
+#define SA_TRACE_OVER_SURVIVORS 1u
+#define SA_TRACE_OVER_CANDIDATES 2u
+#define SA_TRACE_OVER_ENTROPY 4u
+#define SA_TRACE_OVER_SECOND_LEVEL 8u
+#define SA_ROUTE_NONE 0u             /* no survivors */
+#define SA_ROUTE_SPEC_CHAIN 1u       /* the speculative LDS chain delivered the records */
+#define SA_ROUTE_CHAIN_AFTER_SYNC 2u /* the LDS chain, launched once the host knew the survivor count */
+#define SA_ROUTE_LIBRARY_SORTS 3u    /* sort, unique, sort by the library */
+#define SA_ROUTE_RAW 4u              /* sa_extend_hits: the extension stage's own output, unordered */
+#define SA_ROUTE_RM_SORT 5u          /* repeat masker's chain with its final sort */
+#define SA_ROUTE_RM_COVERAGE 6u      /* repeat masker's chain added to the coverage array on the device (no final sort, no download) */
+void sa_get_last_call_trace(sa_call_trace* out);
 void sa_set_count_examined(int on);
 /* X-drop filter kernel selected by InitializeProcessor for plain calls: 0 = exact per-base walk, 1 = fast per-base
  * (7*max(M) <= xdrop), 3 = packed 2-bit/4-bit upper-bound filter. */

@@ -17,6 +17,7 @@ extern "C" {
 
 // ---- introspection --------------------------------------------------------------------------------------------------
 void sa_get_last_call_stats(sa_call_stats* o) { *o = t_stats; }
+void sa_get_last_call_trace(sa_call_trace* o) { *o = t_trace; }
 void sa_set_count_examined(int on) { g_count_examined = on != 0; }
 int sa_get_filter_mode(void) {  // which X-drop filter kernel the next plain (non repeat-masker) call uses
     if (g_count_examined) return g_fast_filter ? 1 : 0;

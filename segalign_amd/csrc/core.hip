@@ -22,6 +22,8 @@ size_t close_seg_gaps(sa_segment_pair* recs, uint32_t* seg_of, const uint32_t* s
 size_t saf_core(DevCtx* dc, Slot* sl, uint32_t num_seeds, const CoreArgs& ca, sa_segment_pair** out) {
     hipStream_t st = sl->stream;
     memset(&t_stats, 0, sizeof(t_stats));
+    memset(&t_trace, 0, sizeof(t_trace));
+    t_trace.rerun_first_batch = t_trace.rerun_last_batch = -1;
     t_stats.num_seeds = num_seeds;
     t_stats.device = dc->index;
 
@@ -131,10 +133,15 @@ size_t saf_core(DevCtx* dc, Slot* sl, uint32_t num_seeds, const CoreArgs& ca, sa
         };
         bool spec_tried = false; // ... was launched (a segment too large for LDS is not worth a second attempt)
         bool spec_done = false;  // the speculative LDS chain of a single-batch call delivered the final records
+        t_trace.segments = (uint32_t)segs.size();
         if (num_hits > 0 && !segs.empty()) {
             // ---- batches of consecutive iterations: expand (find_hits) + extend (find_hsps) ----
-            const uint64_t HIT_BATCH = 1ull << 27;  // 128 Mi hits (1 GiB of 8-byte hits) per batch unless one iteration is larger
-            sl->recA.ensure((size_t)std::max<uint64_t>(1u << 20, std::min<uint64_t>(num_hits, 1ull << 26)), "survivors");
+            const uint64_t HIT_BATCH = g_hit_batch_test ? g_hit_batch_test : 1ull << 27;  // 128 Mi hits (1 GiB of 8-byte hits) per batch unless one iteration is larger
+            // (option out_cap, tests: a small survivor list.  The speculative LDS chain reads up to dedup_seg_max_total() records on the
+            //  DEVICE's count, which the default floor of 2^20 covers: a forced capacity keeps that many records of slack behind its guard)
+            const size_t out_slack = g_out_cap_test ? dedup_seg_max_total() : 0;
+            sl->recA.ensure(g_out_cap_test ? (size_t)g_out_cap_test + out_slack
+                                           : (size_t)std::max<uint64_t>(1u << 20, std::min<uint64_t>(num_hits, 1ull << 26)), "survivors");
             uint32_t it = 0;
             int64_t seed_lo = 0;
             uint64_t hit_lo = 0;
@@ -242,7 +249,7 @@ size_t saf_core(DevCtx* dc, Slot* sl, uint32_t num_seeds, const CoreArgs& ca, sa
                 ea.long_blocks = (uint32_t)g_long_blocks;
                 ea.max_waves = (uint32_t)(ea.fast_filter == 3 ? g_packed_waves : g_max_waves);
                 ea.ent_blocks = 256;  // (grid-stride over a count that lives on the device: a few thousand records usually, millions on repeats)
-                sl->cand_list.ensure((size_t)std::max<uint64_t>(1u << 16, bh / 16), "candidate list");
+                sl->cand_list.ensure(g_cand_cap_test ? (size_t)g_cand_cap_test : (size_t)std::max<uint64_t>(1u << 16, bh / 16), "candidate list");
                 // chain shortcut: valid for the plain X-drop recurrence (xdrop >= 0), kept to query blocks below 2^29 bases on the
                 // general path (the envelope it is tested in; the 64-bit sort key of rounds 1-4 needed it, chain_key32 does not), and
                 // off while E is being counted.  The repeat masker takes it too: its window only decides WHICH
@@ -274,7 +281,7 @@ size_t saf_core(DevCtx* dc, Slot* sl, uint32_t num_seeds, const CoreArgs& ca, sa
                     ea.chain_head_count = &sl->d_cnt->n_heads;
                     ea.chain_big = &sl->d_cnt->n_chain_big;
                 }
-                sl->ent_list.ensure((size_t)std::max<uint64_t>(1u << 16, bh / 32), "entropy list");
+                sl->ent_list.ensure(g_ent_cap_test ? (size_t)g_ent_cap_test : (size_t)std::max<uint64_t>(1u << 16, bh / 32), "entropy list");
                 Counters before = *sl->h_cnt;  // counters as of the previous batch (zero for the first)
                 before.n_long = 0;
                 before.n_ent = 0;
@@ -293,9 +300,10 @@ size_t saf_core(DevCtx* dc, Slot* sl, uint32_t num_seeds, const CoreArgs& ca, sa
                 }
                 before.n_audit = 0;
                 before.n_chain_big = 0;
+                const int batch = (int)t_trace.batches++;
                 for (;;) {  // rerun the batch with larger lists if one overflowed (device writes are guarded)
                     ea.out = sl->recA.p;
-                    ea.out_cap = (uint32_t)std::min<size_t>(sl->recA.cap, 0xFFFFFFFFu);
+                    ea.out_cap = (uint32_t)std::min<size_t>(sl->recA.cap - out_slack, 0xFFFFFFFFu);
                     ea.cand_list = sl->cand_list.p;
                     ea.cand_cap_recs = (uint32_t)std::min<size_t>(sl->cand_list.cap, 0xFFFFFFFFu);
                     ea.ent_list = sl->ent_list.p;
@@ -341,6 +349,7 @@ size_t saf_core(DevCtx* dc, Slot* sl, uint32_t num_seeds, const CoreArgs& ca, sa
                     const uint32_t seg_words = dedup_seg_info_words();
                     if (spec) {
                         spec_tried = true;
+                        t_trace.spec_tried = 1;
                         sl->out16.ensure(dedup_seg_max_total(), "out16");
                         ensure_host_out(dedup_seg_max_total());
                         ensure_host_seg(std::max<size_t>(dedup_seg_max_total(), seg_words));
@@ -354,6 +363,7 @@ size_t saf_core(DevCtx* dc, Slot* sl, uint32_t num_seeds, const CoreArgs& ca, sa
                     check_memcpy(hipMemcpyAsync(sl->h_cnt, sl->d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, st), "counters");
                     check_sync(st, "extend");
                     spec_done = spec && sl->h_seg_info[seg_words - 1] == 0;
+                    t_trace.spec_refused = spec && !spec_done;
                     if (ea.chain_cap && sl->h_cnt->n_long > ea.chain_cap && sl->h_cnt->n_long <= ea.cand_cap_recs) {
                         spec_done = false;  // (the chain ran on an unfinished survivor list)
                         path_flags |= SA_PATH_CHAIN_SLICED;
@@ -370,6 +380,7 @@ size_t saf_core(DevCtx* dc, Slot* sl, uint32_t num_seeds, const CoreArgs& ca, sa
                             check_memcpy(hipMemsetAsync(&sl->d_cnt->n_heads, 0, sizeof(uint32_t), st), "chain heads");
                             { ProfScope p(sl, "chain_group"); launch_chain_group(es, st); }
                             { ProfScope p(sl, "extend_exact_chain"); launch_extend_exact_chain(es, st); }
+                            t_trace.slices++;
                         }
                         { ProfScope p(sl, "extend_entropy"); launch_extend_entropy(ea, st); }
                         check_launch("extend (sliced chain)");
@@ -378,8 +389,14 @@ size_t saf_core(DevCtx* dc, Slot* sl, uint32_t num_seeds, const CoreArgs& ca, sa
                     }
                     const Counters& c = *sl->h_cnt;
                     const bool l2_ok = !(ea.td && ea.td_ctx) || c.n_l2_max <= ea.l2_cap;
+                    t_trace.l2_max = std::max(t_trace.l2_max, c.n_l2_max);
                     if (c.survivors <= ea.out_cap && c.n_long <= ea.cand_cap_recs && c.n_ent <= ea.ent_cap_recs && l2_ok) break;
                     path_flags |= SA_PATH_LIST_REGROWN;
+                    t_trace.reruns++;
+                    if (t_trace.rerun_first_batch < 0) t_trace.rerun_first_batch = batch;
+                    t_trace.rerun_last_batch = batch;
+                    t_trace.overflowed |= (c.survivors > ea.out_cap ? 1u : 0u) | (c.n_long > ea.cand_cap_recs ? 2u : 0u) |
+                                          (c.n_ent > ea.ent_cap_recs ? 4u : 0u) | (l2_ok ? 0u : 8u);
                     if (!l2_ok)  // (the later stages saw a truncated list)
                         sl->l2_list.ensure((size_t)c.n_l2_max * L2_NSUB + ((size_t)c.n_l2_max * L2_NSUB) / 4, "second-level list(grow)");
                     // an overflowing long list also truncates what the later kernels saw: size everything from the
@@ -388,7 +405,7 @@ size_t saf_core(DevCtx* dc, Slot* sl, uint32_t num_seeds, const CoreArgs& ca, sa
                     if (c.n_ent > ea.ent_cap_recs || c.n_long > ea.cand_cap_recs)
                         sl->ent_list.ensure((size_t)std::min<uint64_t>(bh, (uint64_t)c.n_ent + c.n_long), "entropy list(grow)");
                     if (c.survivors > ea.out_cap || c.n_long > ea.cand_cap_recs)
-                        sl->recA.ensure((size_t)std::min<uint64_t>((uint64_t)before.survivors + bh, (uint64_t)c.survivors + c.n_long + c.n_ent),
+                        sl->recA.ensure((size_t)std::min<uint64_t>((uint64_t)before.survivors + bh, (uint64_t)c.survivors + c.n_long + c.n_ent) + out_slack,
                                         "survivors(grow)", true, st);
                     check_memcpy(hipMemcpy(sl->d_cnt, &before, sizeof(Counters), hipMemcpyHostToDevice), "counter reset");
                     cleared = false;  // (the rerun of the batch clears its lists itself)
@@ -419,9 +436,11 @@ size_t saf_core(DevCtx* dc, Slot* sl, uint32_t num_seeds, const CoreArgs& ca, sa
                     check_memcpy(hipMemcpyAsync(sl->h_out + SPEC_RECS, sl->out16.p + SPEC_RECS, (size_t)(survivors - SPEC_RECS) * sizeof(sa_segment_pair),
                                                 hipMemcpyDeviceToHost, st), "hsp_output");
                     check_sync(st, "hsp_output");
+                    t_trace.second_copy = survivors - SPEC_RECS;
                 }
                 n_final = (uint32_t)close_seg_gaps(sl->h_out, sl->h_seg, sl->h_seg_info, (uint32_t)segs.size());
                 have_seg = true;
+                t_trace.route = SA_ROUTE_SPEC_CHAIN;
             } else if (survivors > 0 && ca.raw_hits) {  // the extension stage's own output, unordered
                 sl->out16.ensure(survivors, "out16");
                 ensure_host_out(survivors);
@@ -431,6 +450,7 @@ size_t saf_core(DevCtx* dc, Slot* sl, uint32_t num_seeds, const CoreArgs& ca, sa
                              "hsp_output");
                 check_sync(st, "hsp_output");
                 n_final = survivors;
+                t_trace.route = SA_ROUTE_RAW;
             } else if (survivors > 0) {
                 sl->recB.ensure(std::max<size_t>(survivors, sl->recA.cap), "survivors B");
                 size_t tb = sort_temp_bytes(survivors);
@@ -458,6 +478,7 @@ size_t saf_core(DevCtx* dc, Slot* sl, uint32_t num_seeds, const CoreArgs& ca, sa
                     }
                 }
                 if (!done && !ca.rm && segs.size() <= dedup_small_max_segs() && !g_no_small_dedup) path_flags |= SA_PATH_DEDUP_FALLBACK;
+                t_trace.route = done ? SA_ROUTE_CHAIN_AFTER_SYNC : !ca.rm ? SA_ROUTE_LIBRARY_SORTS : ca.cov_diff ? SA_ROUTE_RM_COVERAGE : SA_ROUTE_RM_SORT;
                 if (done) {
                     // nothing left to do on the device
                 } else if (!ca.rm) {

@@ -477,6 +477,8 @@ extern int g_long_blocks;
 extern int g_packed_waves;
 extern int g_ctx_waves;
 extern uint32_t g_l2_cap_test;
+extern uint32_t g_cand_cap_test, g_ent_cap_test, g_out_cap_test;
+extern uint64_t g_hit_batch_test;
 extern int g_nbr_two_stage;
 extern int g_table_atomic;
 extern int64_t g_arena_gb;
@@ -499,6 +501,7 @@ extern uint32_t CHAIN_CAP;
 extern SeedShape g_shape;
 extern uint32_t g_query_len[SA_BUFFER_DEPTH];
 extern thread_local sa_call_stats t_stats;
+extern thread_local sa_call_trace t_trace;
 extern thread_local std::vector<uint2> t_audit;
 extern thread_local uint32_t t_front_flags;  // SA_PATH_* bits the front of the calling thread's current call has set (front.hip -> core.hip)
 

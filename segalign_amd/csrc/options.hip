@@ -31,6 +31,8 @@ int g_long_blocks = 1792;  // SEGALIGN_AMD_LONG_BLOCKS: grid of the long kernel 
 int g_packed_waves = 4096; // SEGALIGN_AMD_PACKED_WAVES: waves of the packed filter (2 workgroups of 8 waves per CU measured best: 3072 +16 %, 6144 +20 %, 8192 +14 %)
 int g_ctx_waves = 0;       // SEGALIGN_AMD_CTX_WAVES: wave budget of the context filter; 0 = one 4096-hit chunk per wave (measured best)
 uint32_t g_l2_cap_test = 0; // SEGALIGN_AMD_L2_CAP
+uint32_t g_cand_cap_test = 0, g_ent_cap_test = 0, g_out_cap_test = 0;  // options cand_cap / ent_cap / out_cap (tests): first size of the candidate / entropy / survivor list; 0 = the call's own sizing
+uint64_t g_hit_batch_test = 0;  // option hit_batch (tests): hits per batch of the general path; 0 = 2^27
 int g_nbr_two_stage = 1;   // SEGALIGN_AMD_NBR_ONE_STAGE=1: every table entry cuts its own context out of the target
 int g_table_atomic = 0;    // option table_atomic: build the seed table with the atomic counting sort even where the partition build applies
 int64_t g_arena_gb = 40;   // option arena_gb: GiB of table arena the engine starts mapping at InitializeProcessor (0: on demand only)
@@ -56,6 +58,7 @@ SeedShape g_shape = {0, 0, 0, {0}};
 uint32_t g_query_len[SA_BUFFER_DEPTH] = {0, 0};
 
 thread_local sa_call_stats t_stats;
+thread_local sa_call_trace t_trace;  // which branches of saf_core the calling thread's last call took (sa_get_last_call_trace)
 thread_local std::vector<uint2> t_audit;
 thread_local uint32_t t_front_flags = 0;  // rejected hits of the calling thread's last hot call (audit option)
 uint32_t SPEC_RECS = 16384;
@@ -150,6 +153,8 @@ static Option g_opts[] = {
     // test-only: small capacities that force the overflow / fallback branches
     {"l2_cap", 0, 0, 1 << 30, 1}, {"spec_dedup", 1, 0, 1, 1}, {"spec_recs", 16384, 1, 16384, 1}, {"dedup_seg_max", 0, 0, 1 << 30, 1},
     {"q2_limit_mb", 4096, 1, 4096, 1},                 // (tests) bytes the 16 two-bit copies of a query strand may span before calls leave the table-direct path
+    {"cand_cap", 0, 0, 1 << 30, 1}, {"ent_cap", 0, 0, 1 << 30, 1}, {"out_cap", 0, 0, 1 << 26, 1},  // first size of the candidate / entropy / survivor list of a batch (0: sized by the hits); saf_core's rerun loop regrows them
+    {"hit_batch", 0, 0, 1ll << 40, 1},                 // hits per extension batch of the general path (0: 2^27)
     {"no_small_dedup", 0, 0, 1, 1}, {"chain_no_link", 0, 0, 1, 1}, {"chain_cap", 1 << 23, 1, 1 << 30, 1}, {"audit_cap", 0, 0, 1 << 28, 1},
 };
 static Option* find_option(const char* name) {
@@ -223,6 +228,10 @@ void resolve_options() {
     g_gapped_greedy_edges = opt_value("gapped_greedy_edges");
     g_gapped_pieces = opt_value("gapped_pieces");
     g_l2_cap_test = opt_value("l2_cap") ? (uint32_t)std::max<int64_t>(L2_NSUB, opt_value("l2_cap")) : 0u;
+    g_cand_cap_test = (uint32_t)opt_value("cand_cap");
+    g_ent_cap_test = (uint32_t)opt_value("ent_cap");
+    g_out_cap_test = (uint32_t)opt_value("out_cap");
+    g_hit_batch_test = (uint64_t)opt_value("hit_batch");
     g_spec_dedup = (int)opt_value("spec_dedup");
     SPEC_RECS = (uint32_t)opt_value("spec_recs");
     g_dedup_seg_max = (uint32_t)opt_value("dedup_seg_max");

@@ -30,7 +30,7 @@ C_ABI_SYMBOLS = [
     "sa_clear_ref", "sa_generate_shape_pos", "sa_generate_seed_pos_table", "sa_send_query_write_request",
     "sa_clear_query", "sa_seed_and_filter", "sa_seed_and_filter_range", "sa_free_segments",
     "sa_rm_send_query_write_request", "sa_rm_clear_query", "sa_rm_seed_and_filter", "sa_set_max_hits",
-    "sa_get_max_hits", "sa_max_hits_for_mem", "sa_get_last_call_stats", "sa_set_count_examined",
+    "sa_get_max_hits", "sa_max_hits_for_mem", "sa_get_last_call_stats", "sa_get_last_call_trace", "sa_set_count_examined",
     "sa_profile_enable", "sa_profile_reset", "sa_profile_num_entries", "sa_profile_get", "sa_profile_busy_ms", "sa_get_ref_len",
     "sa_get_num_index", "sa_get_index_table_size", "sa_copy_ref_codes", "sa_copy_index_table", "sa_copy_pos_table",
     "sa_copy_query_codes", "sa_get_query_len", "sa_device_make_seeds", "sa_version",
@@ -183,6 +183,16 @@ class CallStats(C.Structure):
                 ("device", C.c_int), ("lookup_path", C.c_int), ("path_flags", C.c_uint32), ("num_forwarded", C.c_uint64)]
 
 
+class CallTrace(C.Structure):  # sa_call_trace
+    _fields_ = [("segments", C.c_uint32), ("batches", C.c_uint32), ("reruns", C.c_uint32), ("rerun_first_batch", C.c_int32),
+                ("rerun_last_batch", C.c_int32), ("overflowed", C.c_uint32), ("slices", C.c_uint32), ("spec_tried", C.c_uint32),
+                ("spec_refused", C.c_uint32), ("second_copy", C.c_uint32), ("route", C.c_uint32), ("l2_max", C.c_uint32)]
+
+
+TRACE_OVER_SURVIVORS, TRACE_OVER_CANDIDATES, TRACE_OVER_ENTROPY, TRACE_OVER_SECOND_LEVEL = 1, 2, 4, 8
+ROUTE_NONE, ROUTE_SPEC_CHAIN, ROUTE_CHAIN_AFTER_SYNC, ROUTE_LIBRARY_SORTS, ROUTE_RAW, ROUTE_RM_SORT, ROUTE_RM_COVERAGE = range(7)
+
+
 class TableBuildInfo(C.Structure):  # sa_table_build_info
     _fields_ = [("build", C.c_int32), ("unsorted_partitions", C.c_uint32), ("nbr_fill", C.c_int32), ("left_skip", C.c_uint32)]
 
@@ -263,6 +273,7 @@ def lib():
     L.sa_max_hits_for_mem.restype = C.c_int
     L.sa_max_hits_for_mem.argtypes = [C.c_uint64]
     L.sa_get_last_call_stats.argtypes = [C.POINTER(CallStats)]
+    L.sa_get_last_call_trace.argtypes = [C.POINTER(CallTrace)]
     L.sa_set_count_examined.argtypes = [C.c_int]
     L.sa_profile_enable.argtypes = [C.c_int]
     L.sa_profile_num_entries.restype = C.c_int
@@ -987,6 +998,13 @@ def last_call_stats():
     return {k: getattr(st, k) for k, _ in CallStats._fields_}
 
 
+def last_call_trace():
+    """Which way the calling thread's last hot call went through the call core (sa_get_last_call_trace; test entry)."""
+    tr = CallTrace()
+    lib().sa_get_last_call_trace(C.byref(tr))
+    return {k: int(getattr(tr, k)) for k, _ in CallTrace._fields_}
+
+
 def lookup_mode():
     """0 general (seed words), 1 table-direct, 2 table-direct with target context (see sa_get_lookup_mode)."""
     return int(lib().sa_get_lookup_mode())
@@ -1169,7 +1187,8 @@ def options():
     out = {}
     for i in range(lib().sa_option_count()):
         t = C.c_int(0)
-        out[lib().sa_option_name(i, C.byref(t)).decode()] = bool(t.value)
+        name = lib().sa_option_name(i, C.byref(t)).decode()  # (first: an assignment evaluates its right side before the subscript)
+        out[name] = bool(t.value)
     return out
 
 

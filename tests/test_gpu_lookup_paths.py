@@ -106,16 +106,32 @@ def test_lookup_paths_under_a_max_hits_split(oracle, clean, mode, env):
                                  {"SEGALIGN_AMD_L2_CAP": "1024"}])        # 4 records per sub-list: overflow, regrow, rerun
 def test_every_output_path_of_a_multi_chunk_call(oracle, clean, env):
     """The ways the survivors of a call can reach the host -- speculative LDS chain with one or two copies, the same chain after
-    a sync, the library-sort fallback -- must all give the oracle's vectors."""
+    a sync, the library-sort fallback -- must all give the oracle's vectors, and the call's trace (sa_get_last_call_trace) must show that
+    the knob changed the way: a knob the engine ignored would leave the speculative chain's single copy."""
     with_env(env)
     t, q = synth.make_pair(200000, 71, 72, sub_rate=0.08, mask_frac=0.1, records=2, indel_every=500)
     c = Case(t, q, chunk=12000).oracle_setup(oracle).engine_setup(clean)
     ch = c.chunks()
     assert len(ch) == 17
     total = 0
+    E = c.E
     for rev in (False, True):
         wants = [c.oracle_saf(c.host_seeds(s, e, rev), rev)[0] for (s, e) in ch]
         outs = c.E.SeedAndFilterChunks(ch[0][0], ch[15][1], rev, 0)
+        st, tr = E.last_call_stats(), E.last_call_trace()
+        assert (tr["segments"], tr["batches"], tr["slices"]) == (32, 1, 0) and st["num_survivors"] > 64, (env, rev, tr)
+        if "SEGALIGN_AMD_SPEC_RECS" in env:
+            assert tr["route"] == E.ROUTE_SPEC_CHAIN and tr["spec_tried"] and tr["second_copy"] == st["num_survivors"] - 8, (rev, st, tr)
+        elif "SEGALIGN_AMD_DEDUP_SEG_MAX" in env:
+            assert tr["route"] == E.ROUTE_LIBRARY_SORTS and tr["spec_tried"] and tr["spec_refused"] and st["path_flags"] & E.PATH_DEDUP_FALLBACK, (rev, st, tr)
+        elif "SEGALIGN_AMD_SPEC_DEDUP" in env:
+            assert tr["route"] == E.ROUTE_CHAIN_AFTER_SYNC and not tr["spec_tried"] and not st["path_flags"] & E.PATH_DEDUP_FALLBACK, (rev, st, tr)
+        elif "SEGALIGN_AMD_NO_SMALL_DEDUP" in env:
+            assert tr["route"] == E.ROUTE_LIBRARY_SORTS and not tr["spec_tried"] and not st["path_flags"] & E.PATH_DEDUP_FALLBACK, (rev, st, tr)
+        else:   # four records per sub-list: the slot's first call overflows the second-level list and reruns; the list stays regrown
+            assert tr["route"] == E.ROUTE_SPEC_CHAIN and tr["second_copy"] == 0 and tr["l2_max"] > 4, (rev, tr)
+            if not rev:
+                assert tr["reruns"] >= 1 and tr["overflowed"] & E.TRACE_OVER_SECOND_LEVEL and st["path_flags"] & E.PATH_LIST_REGROWN, (st, tr)
         for j in range(16):
             assert seg_equal(outs[j], wants[j]), (env, rev, j)
             total += outs[j].size - 1
