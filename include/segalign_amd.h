@@ -1289,6 +1289,135 @@ size_t sa_net_classify(const uint32_t* first, const uint32_t* block_start, const
                        sa_net_class_stats* stats);
 void sa_free_net_class(sa_net_class* classes);
 
+/* ---- carrying intervals through chains to the other axis (additive; restated by tests/lift_model.py) ----------
+ *
+ * sa_lift_intervals maps intervals of one axis through chains to the other axis: for every interval whether a chain carries it, which
+ * one carries it best, and where it lands.  It is the project's own contract in the spirit of UCSC's liftOver of a BED file through
+ * the chains of a net (not claimed to equal it).  Below, "axis" is the axis the intervals live on and "other" the axis they are mapped
+ * to.  The entry reads no sequence and no table: it needs sa_initialize_interface only.
+ *   Input, chains: exactly as sa_net_classify takes them: first[n_chains + 1], block_start[], block_end[] on the axis, oblock_start[],
+ *     oblock_end[] on the other axis (parallel arrays); group[n_chains], the sequence a chain lies on on the axis (NULL: all 0; ids
+ *     are sparse and unsorted); ogroup[n_chains] (NULL: all 0); ostrand[n_chains] (uint8 0 / 1, NULL: all 0): the caller has flipped a
+ *     strand-1 chain into the plus orientation, so its other blocks descend.  At most 1 << 22 chains and 1 << 26 blocks; a chain may
+ *     be empty.
+ *   Input, intervals: iv_group[], iv_start[], iv_end[]: n_intervals <= 1 << 26 half-open intervals with start < end < 2^31, in any
+ *     order; they may overlap and repeat.  iv_group NULL: all 0.
+ *   Input, parameters: p = {num, den}, the least mapped fraction as a ratio (NULL: 95 / 100), 1 <= den <= 1 << 20 and num <= den;
+ *     flags: SA_LIFT_MULTIPLE, SA_LIFT_BLOCKS, both or 0.
+ *   Validation (on the host, one linear pass; a message and exit code 1, like the other entries): the CSR, block, other-block and
+ *     ostrand rules of sa_net_classify (first[0] = 0, first[] non-decreasing, start < end < 2^31, the blocks of a chain ascend and are
+ *     disjoint; on the other axis ostart < oend < 2^31, oend - ostart = end - start, the other blocks of a chain ascend with ostrand 0
+ *     and descend with ostrand 1 and are disjoint; ostrand in 0 .. 1); the interval rule and the limits above; the ratio rules;
+ *     flags <= 3.
+ *   Per interval I = [s, e) of group g, L = e - s, and every chain c with group[c] = g: the clipped blocks of c are its blocks
+ *     intersected with I, and mapped(c) is their bases.  c touches I iff mapped(c) >= 1; c qualifies iff it touches and
+ *     mapped(c) * den >= num * L (in int64).  The image of I through c is first_block, the absolute index of the first clipped block;
+ *     n_blocks, first to last clipped block inclusive; mapped; and the other hull [ostart, oend) of the clipped other blocks, each
+ *     clipped by sa_net_classify's rule: a block that loses dL bases on its left and dR on its right on the axis becomes
+ *     [ostart_k + dL, oend_k - dR) with ostrand 0 and [ostart_k + dR, oend_k - dL) with ostrand 1.  By monotonicity the hull is two of
+ *     the four outer ends of the first and the last clipped block.
+ *   Hit order: the touching chains of an interval ordered by (start of the chain's first block on the axis ascending, chain index
+ *     ascending).
+ *   Status: SA_LIFT_UNMAPPED (0) no chain touches; SA_LIFT_PARTIAL (1) some touch, none qualifies; SA_LIFT_MAPPED (2) exactly one
+ *     qualifies; SA_LIFT_DUPLICATED (3) two or more qualify.
+ *   Best chain: the touching chain with the greatest mapped, among equal values the first in hit order.  Qualifying is monotone in
+ *     mapped, so the best chain qualifies whenever any does.
+ *   Output: (1) one sa_lift_record per interval, in input order: status, n_touch, n_qualify, first_hit, and the best chain's chain,
+ *     ogroup, image and strand (its ostrand); for an unmapped interval chain = 0xFFFFFFFF and the other fields of the best chain are
+ *     0.  (2) sa_lift_hit records, interval after interval, in hit order within an interval: without SA_LIFT_MULTIPLE one hit for every
+ *     MAPPED interval (its one qualifying chain) and none otherwise; with it one hit per qualifying chain of every interval.  first_hit
+ *     is the index of an interval's first hit, defined for every interval as the running count.  (3) With SA_LIFT_BLOCKS one
+ *     sa_lift_block {start, end, ostart, oend} per clipped block of every hit, hit after hit, in the chain's block order; out_block is
+ *     the index of a hit's first one; without the flag none are returned and out_block = 0.  More than 2^31 - 1 hits or output blocks
+ *     end the call with a message.  (4) sa_lift_stats; candidates counts the chains the device tested, summed over the intervals:
+ *     with the chains of a group in hit order (an empty chain counting as the hull (0, 0)), those from the first chain whose hull ends
+ *     after s to the last whose hull starts before e, none if there is no such first chain before that last one.
+ *   Consequences (held by the tests): (a) mapped(c) is the number of bases of I that lie in a block of c.  (b) 0 <= n_qualify <=
+ *     n_touch, and the hull contains every clipped other block.  (c) If the chains of a group have pairwise disjoint hulls on the axis
+ *     (what sa_net_subset with SA_SUBSET_SPLIT returns) and 2 * num > den, no interval is DUPLICATED.  (d) An interval inside one block
+ *     of a strand-0 chain that touches no other chain is MAPPED to an interval of the same length, and lifting that image back with the
+ *     axes exchanged through the same chain returns the interval.  (e) The records do not depend on the flags, and with both flags the
+ *     hits of the MAPPED intervals are those returned without SA_LIFT_MULTIPLE.
+ * The device sorts the chains once by (group, hull start), stable, which is the hit order, and takes a running maximum of the hull ends
+ * per group; three binary searches give an interval the positions that can touch it, one wavefront tests them 64 at a time (hull test,
+ * two binary searches in the chain's blocks, clipped bases from prefix sums, __ballot), a prefix sum of the hit counts places the hits
+ * and one of their n_blocks the blocks.  Slots and thread safety are those of sa_net_chains. */
+#define SA_LIFT_MULTIPLE 1u /* a hit per qualifying chain of every interval, not only the one of a MAPPED interval */
+#define SA_LIFT_BLOCKS 2u   /* also the clipped block pairs of every hit */
+#define SA_LIFT_UNMAPPED 0
+#define SA_LIFT_PARTIAL 1
+#define SA_LIFT_MAPPED 2
+#define SA_LIFT_DUPLICATED 3
+
+typedef struct sa_lift_params { /* 8 bytes */
+    uint32_t num, den; /* a chain qualifies iff mapped * den >= num * (end - start); 1 <= den <= 1 << 20, num <= den */
+} sa_lift_params;
+
+typedef struct sa_lift_record { /* 48 bytes */
+    uint32_t status;      /* SA_LIFT_UNMAPPED, _PARTIAL, _MAPPED, _DUPLICATED */
+    uint32_t n_touch;     /* chains that hold a base of the interval */
+    uint32_t n_qualify;   /* of those, the ones that hold the least fraction */
+    uint32_t first_hit;   /* the index of the interval's first hit: the hits of all earlier intervals */
+    uint32_t chain;       /* the best chain; 0xFFFFFFFF when none touches */
+    uint32_t ogroup;      /* the best chain's */
+    uint32_t ostart, oend; /* the other hull of its clipped blocks */
+    uint32_t mapped;      /* bases of the interval in its blocks */
+    uint32_t first_block; /* absolute index of its first clipped block */
+    uint32_t n_blocks;    /* first to last clipped block inclusive */
+    uint8_t strand;       /* its ostrand */
+    uint8_t pad[3];
+} sa_lift_record;
+
+typedef struct sa_lift_hit { /* 32 bytes */
+    uint32_t interval;
+    uint32_t chain;
+    uint32_t ostart, oend;
+    uint32_t mapped;
+    uint32_t first_block;
+    uint32_t n_blocks;
+    uint32_t out_block; /* with SA_LIFT_BLOCKS the index of the hit's first sa_lift_block, else 0 */
+} sa_lift_hit;
+
+typedef struct sa_lift_block { /* 16 bytes */
+    uint32_t start, end;   /* the clipped block on the axis */
+    uint32_t ostart, oend; /* and on the other axis */
+} sa_lift_block;
+
+typedef struct sa_lift_stats { /* 96 bytes */
+    uint64_t intervals;
+    uint64_t chains;
+    uint64_t blocks;
+    uint64_t candidates;  /* positions tested, summed over the intervals */
+    uint64_t touches;     /* the sum of n_touch */
+    uint64_t n_status[4]; /* intervals per status */
+    uint64_t hits;
+    uint64_t out_blocks;
+    float prep_ms;        /* device time of the prepare step */
+    float lift_ms;        /* device time from the count kernel to the last block, the two read-backs included */
+} sa_lift_stats;
+#ifdef __cplusplus
+static_assert(sizeof(sa_lift_params) == 8, "sa_lift_params is 8 bytes");
+static_assert(sizeof(sa_lift_record) == 48, "sa_lift_record is 48 bytes");
+static_assert(sizeof(sa_lift_hit) == 32, "sa_lift_hit is 32 bytes");
+static_assert(sizeof(sa_lift_block) == 16, "sa_lift_block is 16 bytes");
+static_assert(sizeof(sa_lift_stats) == 96, "sa_lift_stats is 96 bytes");
+#else
+_Static_assert(sizeof(sa_lift_params) == 8, "sa_lift_params is 8 bytes");
+_Static_assert(sizeof(sa_lift_record) == 48, "sa_lift_record is 48 bytes");
+_Static_assert(sizeof(sa_lift_hit) == 32, "sa_lift_hit is 32 bytes");
+_Static_assert(sizeof(sa_lift_block) == 16, "sa_lift_block is 16 bytes");
+_Static_assert(sizeof(sa_lift_stats) == 96, "sa_lift_stats is 96 bytes");
+#endif
+
+/* Returns the number of records, n_intervals.  *records, *hits and *blocks are malloc-ed and released with sa_free_lift; each is NULL
+ * when there are none; *n_hits and *n_blocks say how many there are.  group, ogroup, ostrand, iv_group, p, stats: nullable. */
+size_t sa_lift_intervals(const uint32_t* first, const uint32_t* block_start, const uint32_t* block_end, const uint32_t* oblock_start,
+                         const uint32_t* oblock_end, const uint32_t* group, const uint32_t* ogroup, const uint8_t* ostrand, size_t n_chains,
+                         const uint32_t* iv_group, const uint32_t* iv_start, const uint32_t* iv_end, size_t n_intervals,
+                         const sa_lift_params* p, uint32_t flags, sa_lift_record** records, sa_lift_hit** hits, size_t* n_hits,
+                         sa_lift_block** blocks, size_t* n_blocks, sa_lift_stats* stats);
+void sa_free_lift(sa_lift_record* records, sa_lift_hit* hits, sa_lift_block* blocks);
+
 const char* sa_version(void);
 
 #ifdef __cplusplus

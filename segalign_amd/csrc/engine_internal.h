@@ -17,7 +17,8 @@
 //   api_net.hip        sa_net_chains: the chains of every group netted into fills and gaps on one axis (net.hip)
 //   api_netsubset.hip  sa_net_subset: the fills of a net cut into clipped, rescored sub-chains (netsubset.hip)
 //   api_netclass.hip   sa_net_classify: the fills of a net classed against their parents on the other axis, with duplication and the filter (netclass.hip)
-//   post_host.h        what those six share on the host: event timing, checked launches, buffer carving, caller-owned arrays, trace batches
+//   api_lift.hip       sa_lift_intervals: intervals of one axis carried through chains to the other axis (lift.hip)
+//   post_host.h        what those seven share on the host: event timing, checked launches, buffer carving, caller-owned arrays, trace batches
 //   gapped.hip         kernels of the gapped entries: y-drop extension of a side, trace sweep, path walk (gapped.h)
 //   cover.hip          kernels and rocPRIM steps of the greedy cover index; its sort and scan wrappers also serve api_hspchain.hip (gapped.h)
 //   hspchain.hip       kernels of the chaining DP: rank keys, gather, tile cross / resolve with or without a gap-cost table, group ends,
@@ -27,6 +28,7 @@
 //   net.hip            kernels of the net: priority order, hulls, and a round's search, count and emit, one wavefront per space (net.h)
 //   netsubset.hip      kernels of the net subset: cut marks, clipped members, the cut members' scores, run sums and records (netsubset.h)
 //   netclass.hip       kernels of the net classes: clipped other blocks as sorted events, depth and duplicated length by prefix sums, class, keep (netclass.h)
+//   lift.hip           kernels of the lift: chains sorted by hull start, an interval's candidate range, count, emit and blocks, one wavefront per interval (lift.h)
 //   api_introspect.hip statistics, lookup mode, copies of device state for the tests
 #pragma once
 #include <hip/hip_runtime.h>
@@ -362,6 +364,8 @@ struct Slot {
     DevBuf<uint8_t> net_work, net_round, net_fills, net_space[2];
     DevBuf<uint8_t> netsubset;        // sa_net_subset (api_netsubset.hip, netsubset.hip): the fills, the members' HSPs and everything made of them
     DevBuf<uint8_t> netclass;         // sa_net_classify (api_netclass.hip, netclass.hip): the fills, the blocks of both axes, the events and everything made of them
+    // sa_lift_intervals (api_lift.hip, lift.hip): the chains, the intervals and what is made per interval; the hits; the output blocks
+    DevBuf<uint8_t> lift, lift_hits, lift_out;
     bool early = false;               // taken from the pool that serves sa_chain_hsps before InitializeProcessor (pool.hip)
 };
 

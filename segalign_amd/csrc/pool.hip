@@ -138,6 +138,9 @@ void slot_destroy(Slot& s) {
     for (int i = 0; i < 2; i++) s.net_space[i].release("net spaces");
     s.netsubset.release("net subset");
     s.netclass.release("net class");
+    s.lift.release("lift");
+    s.lift_hits.release("lift hits");
+    s.lift_out.release("lift blocks");
     s.cand_list.release("candidate list");
     s.l2_list.release("second-level list");
     s.audit.release("audit list");

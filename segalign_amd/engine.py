@@ -49,6 +49,7 @@ C_ABI_SYMBOLS = [
     "sa_net_chains", "sa_free_net",
     "sa_net_subset", "sa_free_net_subset",
     "sa_net_classify", "sa_free_net_class",
+    "sa_lift_intervals", "sa_free_lift",
 ]
 IVL_DTYPE = np.dtype([("query_start", "<u4"), ("len", "<u4")])  # struct Segment, repeat_masker_src/graph.h:32-35
 STRAND_PLUS, STRAND_MINUS, STRAND_BOTH = 1, 2, 3
@@ -174,6 +175,28 @@ class NetClassParams(C.Structure):
 class NetClassStats(C.Structure):
     _fields_ = [("fills", C.c_uint64), ("blocks", C.c_uint64), ("events", C.c_uint64), ("ogroups", C.c_uint64), ("n_type", C.c_uint64 * 4),
                 ("kept", C.c_uint64), ("dup_bases", C.c_uint64), ("class_ms", C.c_float), ("pad", C.c_uint32)]
+
+
+LIFT_RECORD_DTYPE = np.dtype([("status", "<u4"), ("n_touch", "<u4"), ("n_qualify", "<u4"), ("first_hit", "<u4"), ("chain", "<u4"),
+                              ("ogroup", "<u4"), ("ostart", "<u4"), ("oend", "<u4"), ("mapped", "<u4"), ("first_block", "<u4"),
+                              ("n_blocks", "<u4"), ("strand", "u1"), ("pad", "u1", (3,))])  # sa_lift_record
+LIFT_HIT_DTYPE = np.dtype([("interval", "<u4"), ("chain", "<u4"), ("ostart", "<u4"), ("oend", "<u4"), ("mapped", "<u4"),
+                           ("first_block", "<u4"), ("n_blocks", "<u4"), ("out_block", "<u4")])  # sa_lift_hit
+LIFT_BLOCK_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("ostart", "<u4"), ("oend", "<u4")])  # sa_lift_block
+LIFT_MULTIPLE, LIFT_BLOCKS = 1, 2
+LIFT_UNMAPPED, LIFT_PARTIAL, LIFT_MAPPED, LIFT_DUPLICATED = 0, 1, 2, 3
+LIFT_NAMES = ("unmapped", "partial", "mapped", "duplicated")
+LIFT_NONE = 0xFFFFFFFF
+
+
+class LiftParams(C.Structure):
+    _fields_ = [("num", C.c_uint32), ("den", C.c_uint32)]
+
+
+class LiftStats(C.Structure):
+    _fields_ = [("intervals", C.c_uint64), ("chains", C.c_uint64), ("blocks", C.c_uint64), ("candidates", C.c_uint64),
+                ("touches", C.c_uint64), ("n_status", C.c_uint64 * 4), ("hits", C.c_uint64), ("out_blocks", C.c_uint64),
+                ("prep_ms", C.c_float), ("lift_ms", C.c_float)]
 
 
 class CallStats(C.Structure):
@@ -377,6 +400,12 @@ def lib():
     L.sa_net_classify.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                   C.c_size_t, C.POINTER(NetClassParams), C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(NetClassStats)]
     L.sa_free_net_class.argtypes = [C.c_void_p]
+    L.sa_lift_intervals.restype = C.c_size_t
+    L.sa_lift_intervals.argtypes = [C.c_void_p] * 8 + [C.c_size_t] + [C.c_void_p] * 3 + [C.c_size_t, C.POINTER(LiftParams), C.c_uint32,
+                                                                                        C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                                                        C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
+                                                                                        C.POINTER(C.c_size_t), C.POINTER(LiftStats)]
+    L.sa_free_lift.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -909,6 +938,42 @@ def net_select(fills, keep):
         raise ValueError("keep: a kept fill whose parent is dropped")
     out["parent"][has] = new[out["parent"][has]]
     return out, index.astype(np.uint32)
+
+
+def LiftIntervals(first, block_start, block_end, oblock_start, oblock_end, iv_start, iv_end, group=None, ogroup=None, ostrand=None,
+                  iv_group=None, min_match=(95, 100), multiple=False, blocks=False):
+    """Intervals of one axis carried through chains to the other axis (sa_lift_intervals; contract in include/segalign_amd.h, DESIGN.md
+    23).  first, block_start, block_end, oblock_start, oblock_end, ogroup, ostrand: the chains as NetClassify takes them (net_blocks,
+    net_other_blocks); group: one uint32 per chain, the sequence it lies on on the axis (None: all 0); iv_start, iv_end: the half-open
+    intervals, iv_group: their sequences (None: all 0); min_match: (num, den), the least fraction of an interval a chain must hold;
+    multiple: a hit per qualifying chain of every interval, not only the one of a MAPPED interval; blocks: also the clipped block pairs
+    of every hit.  -> (LIFT_RECORD_DTYPE records, LIFT_HIT_DTYPE hits, LIFT_BLOCK_DTYPE blocks or None, stats dict).  Needs
+    InitializeInterface only."""
+    f = np.ascontiguousarray(first, dtype=np.uint32)
+    arr = [np.ascontiguousarray(x, dtype=np.uint32) for x in (block_start, block_end, oblock_start, oblock_end)]
+    g, og, ig = (None if x is None else np.ascontiguousarray(x, dtype=np.uint32) for x in (group, ogroup, iv_group))
+    sd = None if ostrand is None else np.ascontiguousarray(ostrand, dtype=np.uint8)
+    ivs, ive = np.ascontiguousarray(iv_start, dtype=np.uint32), np.ascontiguousarray(iv_end, dtype=np.uint32)
+    n = f.size - 1
+    if n < 0 or any(x.size != arr[0].size for x in arr) or arr[0].size < int(f.max()) or any(x is not None and x.size != n for x in (g, og, sd)):
+        raise ValueError("first: one offset per chain and one more; group, ogroup, ostrand: one entry per chain; blocks: first[-1] of each, on both axes")
+    if ivs.size != ive.size or (ig is not None and ig.size != ivs.size):
+        raise ValueError("iv_start, iv_end, iv_group: one entry per interval")
+    p = LiftParams(int(min_match[0]), int(min_match[1]))
+    rec, hit, blk, nh, nb, st = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t(0), C.c_size_t(0), LiftStats()
+    ptr = [x.ctypes.data if x.size else None for x in arr]
+    per_chain = [x.ctypes.data if x is not None and n else None for x in (g, og, sd)]
+    k = lib().sa_lift_intervals(f.ctypes.data, ptr[0], ptr[1], ptr[2], ptr[3], per_chain[0], per_chain[1], per_chain[2], n,
+                                ig.ctypes.data if ig is not None and ig.size else None, ivs.ctypes.data if ivs.size else None,
+                                ive.ctypes.data if ive.size else None, ivs.size, C.byref(p),
+                                (LIFT_MULTIPLE if multiple else 0) | (LIFT_BLOCKS if blocks else 0), C.byref(rec), C.byref(hit), C.byref(nh),
+                                C.byref(blk), C.byref(nb), C.byref(st))
+    res = (_chain_take(rec, k, LIFT_RECORD_DTYPE), _chain_take(hit, nh.value, LIFT_HIT_DTYPE),
+           _chain_take(blk, nb.value, LIFT_BLOCK_DTYPE) if blocks else None)
+    lib().sa_free_lift(rec, hit, blk)
+    stats = _flat(st)
+    stats["n_status"] = [int(x) for x in st.n_status]
+    return res + (stats,)
 
 
 def cigar(ops):

@@ -63,6 +63,9 @@ struct Config {  // src/graph.h:32-76 with the defaults of src/main.cpp:61-124
     bool net_syn = false;         // --gpu_net_syn=...: the synteny filter's thresholds; .net.class and --gpu_net_subset take the kept fills only
     sa_net_class_params net_syn_p = {0, 0, 0, 0, 0, 0};
     bool gpu_net_subset = false;  // --gpu_net_subset (with --gpu_net): a .net.chains file next to every .net file (sa_net_subset), with --gpu_stitch a .net.maf file
+    bool gpu_lift = false;        // --gpu_lift=FILE[,num/den] (with --gpu_net_subset): the BED lines of FILE lifted through every .net.chains file (sa_lift_intervals)
+    std::string lift_bed;
+    sa_lift_params lift_p = {95, 100};
     int gap_open = 400, gap_extend = 30;
     int xdrop = 910, hspthresh = 3000, ydrop = 9430, gappedthresh = -1;
     uint32_t wga_chunk = 250000, lastz_interval = 10000000, seq_block_size = 500000000;
@@ -226,6 +229,56 @@ static void seed_interval(size_t q_block_start, uint32_t q_len /* block_len - se
             }
         }
     }
+}
+
+// ---- --gpu_lift: the BED file, read once ----
+struct BedLine {
+    std::string line;  // as read, without its line end
+    std::string rest;  // what follows the third field, its tab included
+    long record;       // index of the target record named in the first field, -1: none of the target's
+    uint64_t start, end;
+};
+static std::vector<BedLine> bed_lines;
+
+static void load_bed(const std::string& path) {
+    FILE* f = fopen(path.c_str(), "r");
+    if (!f) die(7, "cant open file: %s", path.c_str());
+    std::string line;
+    size_t no = 0;
+    for (int ch = 0; ch != EOF;) {
+        line.clear();
+        while ((ch = fgetc(f)) != EOF && ch != '\n') line.push_back((char)ch);
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (ch == EOF && line.empty()) break;
+        no++;
+        if (line.empty() || line[0] == '#') continue;
+        BedLine b;
+        const size_t t1 = line.find('\t'), t2 = t1 == std::string::npos ? t1 : line.find('\t', t1 + 1);
+        char* endp = nullptr;
+        bool ok = t2 != std::string::npos;
+        if (ok) {
+            b.start = strtoull(line.c_str() + t1 + 1, &endp, 10);
+            ok = endp == line.c_str() + t2 && t2 > t1 + 1;
+        }
+        size_t t3 = std::string::npos;
+        if (ok) {
+            b.end = strtoull(line.c_str() + t2 + 1, &endp, 10);
+            t3 = (size_t)(endp - line.c_str());
+            ok = t3 > t2 + 1 && (t3 == line.size() || line[t3] == '\t') && b.start < b.end;
+        }
+        if (!ok) {
+            fprintf(stderr, "--gpu_lift: %s line %zu is no BED line (name, start, end with start < end, tab-separated)\n", path.c_str(), no);
+            exit(1);
+        }
+        b.line = line;
+        b.rest = line.substr(t3);
+        const std::string name = line.substr(0, t1);
+        b.record = -1;
+        for (size_t c = 0; c < R.chr_name.size() && b.record < 0; c++)
+            if (R.chr_name[c] == name) b.record = (long)c;
+        bed_lines.push_back(b);
+    }
+    fclose(f);
 }
 
 static size_t chr_of(const std::vector<size_t>& starts, size_t pos) {
@@ -438,6 +491,57 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
                     }
                     fclose(f);
                     if (cfg.gpu_stitch) write_stitched(base + ".net.maf", oh, n_oh, smem.data(), sfirst.data(), nsc);
+                    if (cfg.gpu_lift) {  // the BED lines inside this target block through the sub-chains, the query as the other axis
+                        const size_t r_block_end = r_block_start + R.block_len[r_block_index];
+                        std::vector<uint32_t> lbs(n_oh), lbe(n_oh), lobs(n_oh), lobe(n_oh), lgroup(nsc), logroup(nsc), ivg, ivs, ive;
+                        std::vector<size_t> which;  // the lines lifted here
+                        for (size_t k = 0; k < n_oh; k++) {
+                            lbs[k] = oh[k].ref_start;
+                            lbe[k] = oh[k].ref_start + oh[k].len + 1;
+                            lobs[k] = oh[k].query_start;
+                            lobe[k] = oh[k].query_start + oh[k].len + 1;
+                        }
+                        for (size_t c = 0; c < nsc; c++) {
+                            lgroup[c] = (uint32_t)chr_of(R.chr_start, sc[c].ref_start + r_block_start);
+                            logroup[c] = (uint32_t)chr_of(qs, sc[c].query_start + q_block_start);
+                        }
+                        for (size_t k = 0; k < bed_lines.size(); k++) {
+                            const BedLine& b = bed_lines[k];
+                            if (b.record < 0 || b.end > R.chr_len[b.record]) continue;
+                            const size_t s = R.chr_start[b.record] + b.start, e = R.chr_start[b.record] + b.end;
+                            if (s < r_block_start || e > r_block_end) continue;
+                            which.push_back(k);
+                            ivg.push_back((uint32_t)b.record);
+                            ivs.push_back((uint32_t)(s - r_block_start));
+                            ive.push_back((uint32_t)(e - r_block_start));
+                        }
+                        sa_lift_record* lr = nullptr;
+                        sa_lift_hit* lh = nullptr;
+                        sa_lift_block* lb = nullptr;
+                        size_t n_lh = 0, n_lb = 0;
+                        sa_lift_intervals(sfirst.data(), lbs.data(), lbe.data(), lobs.data(), lobe.data(), lgroup.data(), logroup.data(), nullptr, nsc,
+                                          ivg.data(), ivs.data(), ive.data(), which.size(), &cfg.lift_p, 0, &lr, &lh, &n_lh, &lb, &n_lb, nullptr);
+                        std::string lname = base + ".lifted.bed", uname = base + ".unlifted.bed";
+                        FILE* lf = fopen((cfg.outdir + "/" + lname).c_str(), "w");
+                        if (!lf) die(7, "cant open file: %s", lname.c_str());
+                        FILE* uf = fopen((cfg.outdir + "/" + uname).c_str(), "w");
+                        if (!uf) die(7, "cant open file: %s", uname.c_str());
+                        static const char* const reason[4] = {"#Deleted", "#Partially deleted", "", "#Duplicated"};
+                        for (size_t k = 0; k < which.size(); k++) {
+                            const BedLine& b = bed_lines[which[k]];
+                            const sa_lift_record& x = lr[k];
+                            if (x.status == SA_LIFT_MAPPED) {
+                                const size_t qi = x.ogroup;
+                                fprintf(lf, "%s\t%zu\t%zu%s\t%c\n", qn[qi].c_str(), x.ostart + q_block_start - qs[qi], x.oend + q_block_start - qs[qi],
+                                        b.rest.c_str(), rev ? '-' : '+');
+                            } else {
+                                fprintf(uf, "%s\n%s\n", reason[x.status & 3], b.line.c_str());
+                            }
+                        }
+                        fclose(lf);
+                        fclose(uf);
+                        sa_free_lift(lr, lh, lb);
+                    }
                     sa_free_net_subset(oh, sc);
                 }
                 sa_free_net(nf);
@@ -519,6 +623,16 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
     }
 }
 
+static void usage();
+static void usage_lift() {
+    fprintf(stderr,
+            "  --gpu_lift=FILE[,num/den] (with --gpu_net_subset: FILE is a BED file: target record, 0-based start, end, the rest of the line kept\n"
+            "      as it is.  Next to each .net.chains file a .lifted.bed file: every line whose interval lies inside the file's target block and\n"
+            "      of which exactly one sub-chain holds at least num/den of the bases (default 95/100), as query record, start, end within the\n"
+            "      record (of the reverse complement in a .minus file), the rest of the line and the strand of the file, in input order; and an\n"
+            "      .unlifted.bed file: every other such line after a line #Deleted (no sub-chain holds a base of it), #Partially deleted (none\n"
+            "      holds enough) or #Duplicated (several do).  Merging the files of several blocks or strands is the caller's)\n");
+}
 static void usage() {
     fprintf(stderr,
             "Usage: segalign_host target.fa query.fa [data_folder/] [options]\n"
@@ -566,6 +680,7 @@ static void usage() {
             "      min_top_score, as a syn fill lies at most max_far from its parent on the query; a nonSyn fill is dropped, and a dropped\n"
             "      fill takes the fills inside its gaps with it.  The .net.class file then holds the kept fills only, and --gpu_net_subset\n"
             "      works on them: .net.chains and .net.maf are the syntenic net's alignments)\n");
+    usage_lift();
 }
 
 // A gap-cost table in axtChain's linearGap layout (see usage).  The file's form is checked here; the values are checked again by the
@@ -710,6 +825,22 @@ int main(int argc, char** argv) {
         }
         else if (!strcmp(a, "--gpu_net_subset")) cfg.gpu_net_subset = true;
         else if (!strcmp(a, "--gpu_net_class")) cfg.gpu_net_class = true;
+        else if (opt(a, "--gpu_lift", v)) {
+            cfg.lift_bed = v;
+            const size_t comma = v.rfind(',');
+            unsigned long long num = 0, den = 0;
+            char tail = 0;
+            if (comma != std::string::npos && sscanf(v.c_str() + comma + 1, "%llu/%llu%c", &num, &den, &tail) == 2) {
+                if (den < 1 || den > (1ull << 20) || num > den) {
+                    fprintf(stderr, "bad --gpu_lift=%s (num/den with 1 <= den <= 1048576 and num <= den)\n", v.c_str());
+                    return 1;
+                }
+                cfg.lift_p = {(uint32_t)num, (uint32_t)den};
+                cfg.lift_bed = v.substr(0, comma);
+            }
+            if (cfg.lift_bed.empty()) { fprintf(stderr, "bad --gpu_lift=%s (a BED file)\n", v.c_str()); return 1; }
+            cfg.gpu_lift = true;
+        }
         else if (opt(a, "--gpu_net_syn", v)) {
             long long t[5];
             char tail = 0;
@@ -746,6 +877,7 @@ int main(int argc, char** argv) {
     if (cfg.gpu_net && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_net needs --gpu_chain_all\n"); return 1; }
     if (cfg.gpu_net_subset && !cfg.gpu_net) { fprintf(stderr, "--gpu_net_subset needs --gpu_net and --gpu_chain_all\n"); return 1; }
     if (cfg.gpu_net_class && !cfg.gpu_net) { fprintf(stderr, "%s needs --gpu_net and --gpu_chain_all\n", cfg.net_syn ? "--gpu_net_syn" : "--gpu_net_class"); return 1; }
+    if (cfg.gpu_lift && !cfg.gpu_net_subset) { fprintf(stderr, "--gpu_lift needs --gpu_net_subset, --gpu_net and --gpu_chain_all\n"); return 1; }
     if (cfg.net_fill_set && !cfg.gpu_net) { fprintf(stderr, "--gpu_net_fill needs --gpu_net and --gpu_chain_all\n"); return 1; }
     cfg.target = pos[0];
     cfg.query = pos[1];
@@ -781,6 +913,7 @@ int main(int argc, char** argv) {
     load_set(cfg.query, Q, true, "query");
     fprintf(stderr, "\nReading target file ...\n");
     load_set(cfg.target, R, false, "ref");
+    if (cfg.gpu_lift) load_bed(cfg.lift_bed);
     auto t1 = std::chrono::steady_clock::now();
     fprintf(stderr, "\nStart alignment ...\n");
 

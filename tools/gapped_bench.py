@@ -43,9 +43,16 @@ the line then adds the fills per class, clipped blocks, events, the sum of odup,
 launches (the sort's come on top) and class ms, the least of the repeats, beside net ms and, with --net-subset, subset ms.  The records
 and counts of both calls are checked against the model (tests/net_class_model.py) once per run.
 
+With --lift[=N] (which implies --net-subset) N intervals (default 1 << 20) drawn from the target with a fixed seed, a third each points,
+100-base and 10 000-base intervals, go through sa_lift_intervals with the query as the other axis, once through the
+sub-chains of sa_net_subset and once through all chains: the line then adds per chain set the intervals per status, the candidates per
+interval, the hits, and prep ms and lift ms, each the least of the repeats, beside net ms and subset ms, and the entry's own kernel
+launches (the sort's and the running maximum's come on top).  The records, hits and blocks of a 4 096-interval sample through the
+sub-chains, under both flags, are checked against the model (tests/lift_model.py) once per run.
+
   python tools/gapped_bench.py [--workloads standin,lumpy] [--repeat 3] [--align] [--greedy] [--batches 1024,2048,...]
                                [--pieces N] [--max-extent M] [--chain] [--chain-pen D,A] [--chain-costs T] [--chain-all] [--chain-min N] [--stitch] [--stitch-max-link N]
-                               [--net] [--net-space N] [--net-fill N] [--net-subset] [--net-class] [--net-class-filter S,T,Z,A,F]
+                               [--net] [--net-space N] [--net-fill N] [--net-subset] [--net-class] [--net-class-filter S,T,Z,A,F] [--lift[=N]]
 """
 import argparse
 import functools
@@ -273,9 +280,54 @@ def class_fields(hsps, mem, first, bs, be, fills, repeat, thresholds, net_ms, su
             "class_model_s": round(model_s, 1)}
 
 
+def lift_fields(hsps, mem, first, bs, be, fills, repeat, n, pen, net_ms, subset_ms):
+    """sa_lift_intervals on n intervals of the target (fixed seed; points, 100-base and 10 000-base intervals a third each), through the
+    sub-chains of the net and through all chains, per chain set the least prep and lift time; a 4 096-interval sample through the
+    sub-chains, under both flags, checked against the model."""
+    import lift_model as LM
+    out, sub, _ = E.NetSubset(hsps, mem, first, fills, False, 0, axis="target", split=True, diag_pen=pen[0], anti_pen=pen[1])
+    smem, sfirst = E.subset_csr(sub)
+    sets = {"sub": (sfirst,) + E.net_blocks(out, smem, sfirst, axis="target") + E.net_blocks(out, smem, sfirst, axis="query"),
+            "all": (first, bs, be) + E.net_other_blocks(hsps, mem, first, axis="target")}
+    rng = np.random.default_rng(2323)
+    top = int(be.max()) if be.size else 1 << 20
+    length = np.repeat(np.array([1, 100, 10_000], dtype=np.int64), (n + 2) // 3)[:n]
+    start = (rng.random(n) * np.maximum(top - length, 1)).astype(np.int64)
+    order = rng.permutation(n)
+    start, end = start[order].astype(np.uint32), (start + length)[order].astype(np.uint32)
+    res = {"lift_intervals": int(n), "lift_launches": 11, "lift_launches_blocks": 15,  # block_len, keys, gather, count, emit (blocks); two (three) scans of three
+           "lift_net_ms": round(net_ms, 3), "lift_subset_ms": None if subset_ms is None else round(subset_ms, 3)}
+    for name, c in sets.items():
+        prep = lift = wall = None
+        for _ in range(repeat):
+            t0 = time.perf_counter()
+            rec, hits, _, st = E.LiftIntervals(*c, start, end)
+            w = (time.perf_counter() - t0) * 1e3
+            prep = st["prep_ms"] if prep is None else min(prep, st["prep_ms"])
+            lift = st["lift_ms"] if lift is None else min(lift, st["lift_ms"])
+            wall = w if wall is None else min(wall, w)
+        res.update({"lift_%s_chains" % name: int(st["chains"]), "lift_%s_blocks" % name: int(st["blocks"]),
+                    **{"lift_%s_%s" % (name, s): int(st["n_status"][k]) for k, s in enumerate(LM.NAMES)},
+                    "lift_%s_candidates_per_interval" % name: round(st["candidates"] / max(n, 1), 3),
+                    "lift_%s_touches_per_interval" % name: round(st["touches"] / max(n, 1), 3), "lift_%s_hits" % name: int(st["hits"]),
+                    "lift_%s_prep_ms" % name: round(prep, 3), "lift_%s_ms" % name: round(lift, 3), "lift_%s_call_ms" % name: round(wall, 3)})
+    t0 = time.perf_counter()
+    k = min(n, 4096)
+    got = E.LiftIntervals(*sets["sub"], start[:k], end[:k], multiple=True, blocks=True)
+    want = LM.lift(*sets["sub"], start[:k], end[:k], multiple=True, blocks=True)
+    try:
+        LM.same(got, want)
+        LM.same_stats(got[3], want[3])
+    except AssertionError as ex:
+        raise SystemExit("sa_lift_intervals differs from the model: %s" % (ex,))
+    res.update({"lift_model_checked": True, "lift_model_intervals": int(k), "lift_model_s": round(time.perf_counter() - t0, 1)})
+    return res
+
+
 def net_fields(hsps, chains, members, repeat, net, peel_ms, dp_ms, pen=(0, 0)):
     """sa_net_chains on the kept chains' target blocks, the run with the least net time, checked against the model; net[2]: also
-    subset_fields on its fills; net[3]: also class_fields on them, under the thresholds net[4]."""
+    subset_fields on its fills; net[3]: also class_fields on them, under the thresholds net[4]; net[5]: also lift_fields on so many
+    intervals."""
     import net_model as N
     mem, first = E.chain_csr(members)
     bs, be = E.net_blocks(hsps, mem, first, axis="target")
@@ -295,6 +347,8 @@ def net_fields(hsps, chains, members, repeat, net, peel_ms, dp_ms, pen=(0, 0)):
     extra = subset_fields(hsps, mem, first, fills, repeat, pen, st["net_ms"], peel_ms) if len(net) > 2 and net[2] else {}
     if len(net) > 3 and net[3]:
         extra.update(class_fields(hsps, mem, first, bs, be, fills, repeat, net[4], st["net_ms"], extra.get("subset_ms")))
+    if len(net) > 5 and net[5]:
+        extra.update(lift_fields(hsps, mem, first, bs, be, fills, repeat, net[5], pen, st["net_ms"], extra.get("subset_ms")))
     return {**extra, "net_min_space": int(net[0]), "net_min_fill": int(net[1]), "net_chains": int(st["chains"]), "net_blocks": int(st["blocks"]),
             "net_fills": int(st["fills"]), "net_rounds": int(st["rounds"]), "net_spaces": int(st["spaces"]), "net_max_depth": int(st["max_depth"]),
             "net_chains_without_fill": int(st["chains"] - st["filled"]), "net_prep_ms": round(st["prep_ms"], 3), "net_ms": round(st["net_ms"], 3),
@@ -477,7 +531,12 @@ def main():
     ap.add_argument("--net-class", action="store_true", help="also class the fills against their parents on the query (sa_net_classify); implies --net")
     ap.add_argument("--net-class-filter", default="3000,5000,30,25,100000",
                     help="with --net-class: min_score,min_top_score,min_size,min_ali,max_far of the filtered call")
+    ap.add_argument("--lift", type=int, nargs="?", const=1 << 20, default=0, metavar="N",
+                    help="also lift N intervals of the target through the sub-chains and through all chains (sa_lift_intervals); implies --net-subset")
     a = ap.parse_args()
+    if a.lift < 0 or a.lift > 1 << 26:
+        ap.error("--lift takes 1 .. 1 << 26 intervals")
+    a.net_subset = a.net_subset or a.lift > 0
     a.net = a.net or a.net_subset or a.net_class
     class_filter = tuple(int(x) for x in a.net_class_filter.split(","))
     if len(class_filter) != 5:
@@ -491,7 +550,7 @@ def main():
     for name in a.workloads.split(","):
         if not a.batches:
             print(json.dumps(run(name, a.repeat, a.align, a.greedy, pieces=a.pieces, chain=chain, chain_all_min=a.chain_min if a.chain_all else None,
-                                 stitch=a.stitch_max_link if a.stitch else None, net=(a.net_space, a.net_fill, a.net_subset, a.net_class, class_filter) if a.net else None,
+                                 stitch=a.stitch_max_link if a.stitch else None, net=(a.net_space, a.net_fill, a.net_subset, a.net_class, class_filter, a.lift) if a.net else None,
                                  chain_costs=a.chain_costs or None)), flush=True)
             continue
         for b in a.batches.split(","):
