@@ -920,6 +920,116 @@ size_t sa_chain_hsps_all_costs(const sa_segment_pair* hsps, size_t n, const uint
                                sa_chain_node** nodes, uint32_t** chain_of, sa_chain_all_stats* stats);
 int sa_chain_gap_preset(const char* name, sa_chain_gap_costs* out);
 
+/* ---- chaining under an overlap allowance (additive; restated by tests/hsp_chain_overlap_model.py) ----------
+ *
+ * sa_chain_hsps_ovl and sa_chain_hsps_all_ovl are sa_chain_hsps_costs and sa_chain_hsps_all_costs under a wider predecessor relation:
+ * two HSPs that share a few bases on either axis, as ungapped HSPs on the two sides of an indel usually do, may still link, and the
+ * link is charged for the shared bases.  In the spirit of axtChain, whose DP lets blocks overlap; this project's own contract, not
+ * claimed to equal axtChain.  With bases_x = len_x + 1:
+ *   Overlap: o(j, i) = max(0, re_j - rs_i, qe_j - qs_i).
+ *   Predecessor: j < i iff group[j] == group[i], o(j, i) <= max_overlap and 2 * o(j, i) < min(bases_j, bases_i), and max_gap (below)
+ *     holds.  For o = 0 this is sa_chain_hsps's relation.
+ *     Rank order stays an evaluation order, j < i implies rs_j < rs_i: o >= re_j - rs_i gives rs_i >= rs_j + bases_j - o, and
+ *     2 o < bases_j gives bases_j - o > 0.  (The same two lines on the query axis give qs_j < qs_i.)
+ *     A member that is overlapped at both ends keeps at least one base once each overlap is cut: 2 o1 < bases and 2 o2 < bases give
+ *     o1 + o2 < bases.
+ *   Gaps: those left once o bases are cut off i's head, gap_r = rs_i + o - re_j and gap_q = qs_i + o - qe_j, both >= 0 and at least
+ *     one of them 0 when o > 0.  max_gap (gap_r <= max_gap and gap_q <= max_gap), the linear term anti_pen * (gap_r + gap_q) and the
+ *     gap-cost table gapcost(gap_r, gap_q), its choice of case by a zero gap included, are applied to these.  The diagonal term
+ *     diag_pen * |(rs_i - qs_i) - (rs_j - qs_j)| is unchanged.  pen'(j, i) is the sum of the three.
+ *   Overlap charge: c(j, i) = (o * min(w_j, w_i)) >> 16 with w_x = floor(65536 * max(score_x, 0) / bases_x): the o bases are charged
+ *     at the lower of the two HSPs' average score per base, and an HSP of score <= 0 charges nothing.  One division per HSP, none per
+ *     pair.  Bound: max(score, 0) < 2^31, so w < 2^47; o <= 2^12, so o * w < 2^12 * 2^47 = 2^59, and c < 2^43.  The trimmed gaps are
+ *     below 2^32 + 2^12, so the linear terms stay < 2^54, a gap cost < 2^45 and |f| <= 2^53: every intermediate stays inside +-2^56.
+ *   Candidate value of j for i: f(j) - pen'(j, i) - c(j, i).
+ *   Recurrence, rank, ties, min_score, members, nodes, peel and stats are those of sa_chain_hsps, sa_chain_hsps_all and
+ *     sa_chain_hsps_costs, word for word.  Where a chain has an overlapping link, f is an estimate: the charge stands in for the
+ *     bases that trimming the overlap at the best crossover would remove.
+ *   Validation (a message and exit code 1, like the other entries): max_overlap <= 4096, reserved == 0; p and g as before.
+ * ov == NULL or max_overlap == 0 is exactly sa_chain_hsps_costs / sa_chain_hsps_all_costs (and with g == NULL sa_chain_hsps /
+ * sa_chain_hsps_all): same kernels, same results.  Members of a returned chain may overlap: sa_stitch_chains and the entries behind
+ * it refuse such a chain until its overlaps are trimmed. */
+#define SA_CHAIN_MAX_OVERLAP 4096
+typedef struct sa_chain_overlap {
+    uint32_t max_overlap; /* the most bases two linked HSPs may share on an axis, 0 .. 4096; 0: none */
+    uint32_t reserved;    /* must be 0 */
+} sa_chain_overlap;
+#ifdef __cplusplus
+static_assert(sizeof(sa_chain_overlap) == 8, "sa_chain_overlap is 8 bytes");
+#else
+_Static_assert(sizeof(sa_chain_overlap) == 8, "sa_chain_overlap is 8 bytes");
+#endif
+
+size_t sa_chain_hsps_ovl(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p, const sa_chain_gap_costs* g,
+                         const sa_chain_overlap* ov, sa_chain_member** members, sa_chain_node** nodes, sa_chain_stats* stats);
+size_t sa_chain_hsps_all_ovl(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p,
+                             const sa_chain_gap_costs* g, const sa_chain_overlap* ov, sa_chain_record** chains, size_t* n_chains,
+                             sa_chain_all_member** members, sa_chain_node** nodes, uint32_t** chain_of, sa_chain_all_stats* stats);
+
+/* ---- trimming the overlaps of chains at the best crossover (additive; restated by tests/chain_trim_model.py) ----------
+ *
+ * sa_trim_chains takes chains whose consecutive members may overlap, as sa_chain_hsps_ovl / sa_chain_hsps_all_ovl return them, and
+ * cuts every overlap where the two members together score best, with the sequences in hand.  It needs a resident target block and
+ * query buffer, like sa_stitch_chains, whose errors it gives without one.
+ *   Input: the HSPs; the chains in CSR form as sa_stitch_chains takes them (members[first[c] .. first[c + 1]) are chain c's HSP
+ *     indices in chain order); rev, buffer; p (diag_pen, anti_pen; max_gap and min_score are not read) and g as for
+ *     sa_chain_hsps_costs; flags: SA_TRIM_LINKS or 0.
+ *   Validation (a message and exit code 1): at most 1 << 22 chains and 1 << 22 member entries, first[] as for sa_stitch_chains; every
+ *     member names an HSP of the input that lies inside the block; consecutive members j, i satisfy sa_chain_hsps_ovl's relation with
+ *     max_overlap = 4096 but for group and max_gap: o(j, i) <= 4096 and 2 o < min(bases_j, bases_i); p and g as for the chaining
+ *     entries.
+ *   Crossover, for a link with o > 0: a_k is the substitution score of j's k-th column among its last o columns and b_k that of i's
+ *     k-th column among its first o (sub_mat over the resident codes, as sa_stitch_chains scores a member's column).  x in 0 .. o
+ *     maximises S(x) = sum_{k < x} a_k + sum_{k >= x} b_k; the lowest x wins among equals.  j loses its last o - x columns, i its first x.
+ *     A link with o = 0 has x = 0 and cuts nothing.
+ *   Output: one sa_segment_pair per member entry, in entry order, so that the caller goes on with members = 0 .. M - 1 and first
+ *     unchanged.  A member that loses no column is its input HSP bit for bit.  A cut member has ref_start, query_start moved by what
+ *     its head lost and len shortened by what head and tail lost (at least one base is left), and its score is the sum of sub_mat over
+ *     its remaining columns, exactly.  After trimming, consecutive members satisfy re <= rs' and qe <= qs', sa_chain_hsps's relation.
+ *     Per chain: score = the sum of its returned members' scores minus the sum over its links of pen'(j, i) of sa_chain_hsps_ovl
+ *     (the diagonal term, anti_pen and the table on gap_r = rs_i + o - re_j and gap_q = qs_i + o - qe_j, which are the gaps between the
+ *     trimmed members; no overlap charge), the links with o > 0 and the bases cut.  With SA_TRIM_LINKS one record per link in entry order. */
+#define SA_TRIM_LINKS 1u
+typedef struct sa_trim_chain {
+    int64_t score;          /* exact: member scores less the links' penalties */
+    uint32_t trimmed_links; /* links with o > 0 */
+    uint32_t bases_cut;     /* columns removed from the chain's members: the sum of o over its links */
+} sa_trim_chain;
+
+typedef struct sa_trim_link {
+    uint32_t o;     /* the overlap */
+    uint32_t x;     /* the crossover: i loses x columns, j loses o - x */
+    uint32_t gap_r; /* the gaps between the trimmed members */
+    uint32_t gap_q;
+} sa_trim_link;
+
+typedef struct sa_trim_stats {
+    uint64_t chains;
+    uint64_t members;        /* member entries */
+    uint64_t links;
+    uint64_t trimmed_links;
+    uint64_t cut_members;    /* entries that lost a column and were rescored */
+    uint64_t bases_cut;
+    double kernel_ms;        /* the crossover and the rescoring kernels */
+} sa_trim_stats;
+#ifdef __cplusplus
+static_assert(sizeof(sa_trim_chain) == 16, "sa_trim_chain is 16 bytes");
+static_assert(sizeof(sa_trim_link) == 16, "sa_trim_link is 16 bytes");
+static_assert(sizeof(sa_trim_stats) == 56, "sa_trim_stats is 56 bytes");
+#else
+_Static_assert(sizeof(sa_trim_chain) == 16, "sa_trim_chain is 16 bytes");
+_Static_assert(sizeof(sa_trim_link) == 16, "sa_trim_link is 16 bytes");
+_Static_assert(sizeof(sa_trim_stats) == 56, "sa_trim_stats is 56 bytes");
+#endif
+
+/* Returns the number of member entries M.  *out_hsps (M entries), *chains (n_chains entries) and, with SA_TRIM_LINKS, *links (*n_links
+ * entries; links and n_links nullable otherwise) are malloc-ed and released with sa_free_trim; each is NULL when it would be empty.
+ * p: NULL takes the defaults; g: NULL for no table; stats: nullable.  Slots and thread safety are those of sa_stitch_chains. */
+size_t sa_trim_chains(const sa_segment_pair* hsps, size_t n_hsps, const uint32_t* members, const uint32_t* first, size_t n_chains, int rev,
+                      uint32_t buffer, const sa_chain_params* p, const sa_chain_gap_costs* g, uint32_t flags, sa_segment_pair** out_hsps,
+                      sa_trim_chain** chains, sa_trim_link** links, size_t* n_links, sa_trim_stats* stats);
+void sa_free_trim(sa_segment_pair* out_hsps, sa_trim_chain* chains, sa_trim_link* links);
+
 /* ---- stitching the members of a chain into one gapped alignment (additive; restated by tests/cpp/stitch_check.c and
  *      tests/stitch_model.py) ----------------------------------------------------------------------------------------------
  *

@@ -9,8 +9,8 @@ LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libsegalign_hip.so")
 SOURCES = ["encode.hip", "scan.hip", "table.hip", "seeds.hip", "probe.hip", "extend.hip", "dedup.hip", "coverage.hip",
            "arena.hip", "options.hip", "profile.hip", "pool.hip", "front.hip", "core.hip", "api_setup.hip", "api_calls.hip", "api_rm.hip",
-           "api_introspect.hip", "gapped.hip", "cover.hip", "api_gapped.hip", "hspchain.hip", "hsppeel.hip", "api_hspchain.hip",
-           "stitch.hip", "api_stitch.hip", "net.hip", "api_net.hip", "netsubset.hip",
+           "api_introspect.hip", "gapped.hip", "cover.hip", "api_gapped.hip", "hspchain.hip", "hsppeel.hip", "hspovl.hip", "api_hspchain.hip",
+           "stitch.hip", "api_stitch.hip", "chaintrim.hip", "api_chaintrim.hip", "net.hip", "api_net.hip", "netsubset.hip",
            "api_netsubset.hip", "netclass.hip", "api_netclass.hip", "lift.hip", "api_lift.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 

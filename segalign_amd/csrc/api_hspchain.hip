@@ -1,6 +1,8 @@
 // api_hspchain.hip -- C-ABI sa_chain_hsps: the best collinear chain of every group of HSPs (contract: include/segalign_amd.h),
 // and sa_chain_hsps_all: all chains of every group, peeled best first; sa_chain_hsps_costs and sa_chain_hsps_all_costs:
-// the two under a piecewise-linear gap-cost table, which only hands the DP's launches the table's device image.
+// the two under a piecewise-linear gap-cost table, which only hands the DP's launches the table's device image;
+// sa_chain_hsps_ovl and sa_chain_hsps_all_ovl: the two under an overlap allowance, which makes the node weights and picks
+// hspovl.hip's launchers for the DP.
 // The host side: checks, the slot, rank (two stable radix sorts) and the tile loop (hspchain.hip: cross, resolve), shared by both; then
 // sa_chain_hsps's finish (group starts, ends, members, nodes) or the peel (hsppeel.hip: subtree minimum, chain order, members), and the
 // counts the kernels' work is reported by.
@@ -39,8 +41,9 @@ struct ChainDp {
 
 // The slot's buffers, the upload, rank and the DP (spans 0 and 1 of ev) for n > 0 HSPs on the slot d.sl.  Returns with the stream
 // synchronised, G known and st's pair_evals and tile_steps counted.
-void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, uint32_t T, const CostImage& costs, ChainDp& d, ChainTimer& ev,
-                 sa_chain_stats& st) {
+// max_overlap != 0: the DP runs under the overlap allowance (hspovl.hip), on node weights made after the rank step.
+void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, uint32_t T, const CostImage& costs, uint32_t max_overlap, ChainDp& d,
+                 ChainTimer& ev, sa_chain_stats& st) {
     const uint32_t N = (uint32_t)n, tiles = (N + T - 1) / T;
     d.N = N;
     Slot* sl = d.sl;
@@ -49,13 +52,15 @@ void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, u
     sa_segment_pair* d_hsps;
     uint32_t *d_group, *idx_a, *rs, *qs, *ln, *gr, *pred, *first, *d_image;
     int32_t* sc;
-    int64_t* f;
+    int64_t *f, *ovl_w = nullptr;
+    uint32_t* ovl_lim = nullptr;
     carve(sl->hspchain_work, "hsp chain", [&](Carve& c) {
         c.take(d_hsps, N).take(d_group, N).take(d.key_a, N).take(d.key_b, N).take(idx_a, N).take(d.idx_b, N);
         c.take(rs, N).take(qs, N).take(ln, N).take(gr, N).take(sc, N).take(f, N).take(pred, N);
         c.take(d.head, (size_t)N + 1).take(d.gidx, (size_t)N + 1).take(first, tiles);
         c.take(d.gstart, N).take(d.gend, N).take(d.glen, (size_t)N + 1).take(d.goff, (size_t)N + 1);
         c.take(d.d_members, N).take(d.d_nodes, N).take(d_image, HSPCOST_WORDS);
+        if (max_overlap) c.take(ovl_w, N).take(ovl_lim, N);
     });
     if (!group) d_group = nullptr;
     sl->hspchain_partial.ensure((size_t)tiles * T * sizeof(HspChainPartial), "hsp chain partials");
@@ -90,6 +95,7 @@ void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, u
         cover_sort_anchors(temp, &d.temp_bytes, d.key_a, d.key_b, d.idx_b, idx_a, N, s);
         launch_hspchain_gather(d_hsps, d_group, idx_a, N, rs, qs, ln, sc, gr, d.head, s);
         launch_hspchain_first(gr, N, T, first, s);
+        if (max_overlap) launch_hspovl_weight(a, max_overlap, ovl_w, ovl_lim, s);
     });
     ev.mark(1);
     check_memcpy(hipMemcpyAsync(h_first.data(), first, tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "hsp chain: first tiles");
@@ -97,6 +103,7 @@ void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, u
     d.order = idx_a;
 
     // the DP: tile b after every tile before it
+    const HspOvlNodes ovl = {ovl_w, ovl_lim};
     ev.mark(2);
     for (uint32_t b = 0; b < tiles; b++) {
         const uint32_t c0 = h_first[b], nb = std::min(T, N - b * T);
@@ -105,12 +112,14 @@ void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, u
             exit(15);
         }
         if (b > c0) {
-            ProfScope ps(sl, image ? "hspcost_cross" : "hspchain_cross");
-            launch_hspchain_cross(a, b, c0, partial, image, s);
+            ProfScope ps(sl, max_overlap ? "hspovl_cross" : image ? "hspcost_cross" : "hspchain_cross");
+            if (max_overlap) launch_hspovl_cross(a, ovl, b, c0, partial, image, s);
+            else launch_hspchain_cross(a, b, c0, partial, image, s);
         }
         {
-            ProfScope ps(sl, image ? "hspcost_resolve" : "hspchain_resolve");
-            launch_hspchain_resolve(a, b, c0, partial, image, s);
+            ProfScope ps(sl, max_overlap ? "hspovl_resolve" : image ? "hspcost_resolve" : "hspchain_resolve");
+            if (max_overlap) launch_hspovl_resolve(a, ovl, b, c0, partial, image, s);
+            else launch_hspchain_resolve(a, b, c0, partial, image, s);
         }
         check_launch("hspchain tile");
         st.pair_evals += (uint64_t)(b - c0) * T * nb + (uint64_t)nb * (nb - 1) / 2;
@@ -135,8 +144,16 @@ uint32_t checked(const sa_chain_params* p, size_t n, sa_chain_params& P) {
     return (uint32_t)tile_opt;
 }
 
+// The allowance of a sa_chain_overlap, checked; nullptr is 0, the plain DP.
+uint32_t checked_overlap(const sa_chain_overlap* ov) {
+    if (!ov) return 0;
+    if (ov->max_overlap > SA_CHAIN_MAX_OVERLAP) bad("max_overlap", ov->max_overlap);
+    if (ov->reserved != 0) bad("reserved", ov->reserved);
+    return ov->max_overlap;
+}
+
 size_t chain_hsps(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p, const sa_chain_gap_costs* g,
-                  sa_chain_member** members, sa_chain_node** nodes, sa_chain_stats* stats) {
+                  const sa_chain_overlap* ov, sa_chain_member** members, sa_chain_node** nodes, sa_chain_stats* stats) {
     *members = nullptr;
     if (nodes) *nodes = nullptr;
     sa_chain_stats st;
@@ -147,11 +164,12 @@ size_t chain_hsps(const sa_segment_pair* hsps, size_t n, const uint32_t* group, 
     const uint32_t T = checked(p, n, d.P);
     CostImage costs;
     checked_costs("ChainHsps", g, costs);
+    const uint32_t max_overlap = checked_overlap(ov);
     if (n == 0) return 0;
     Slot* sl = d.sl = acquire_slot_early();
     hipStream_t s = sl->stream;
     ChainTimer ev(s, "hsp chain timing");
-    rank_and_dp(hsps, n, group, T, costs, d, ev, st);
+    rank_and_dp(hsps, n, group, T, costs, max_overlap, d, ev, st);
     const uint32_t G = d.G;
 
     // finish: every group's end and chain length, then the members and the nodes
@@ -192,7 +210,7 @@ size_t chain_hsps(const sa_segment_pair* hsps, size_t n, const uint32_t* group, 
 }
 
 size_t chain_hsps_all(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p, const sa_chain_gap_costs* g,
-                      sa_chain_record** chains, size_t* n_chains, sa_chain_all_member** members, sa_chain_node** nodes, uint32_t** chain_of,
+                      const sa_chain_overlap* ov, sa_chain_record** chains, size_t* n_chains, sa_chain_all_member** members, sa_chain_node** nodes, uint32_t** chain_of,
                       sa_chain_all_stats* stats) {
     *chains = nullptr;
     *n_chains = 0;
@@ -207,11 +225,12 @@ size_t chain_hsps_all(const sa_segment_pair* hsps, size_t n, const uint32_t* gro
     const uint32_t T = checked(p, n, d.P);
     CostImage costs;
     checked_costs("ChainHsps", g, costs);
+    const uint32_t max_overlap = checked_overlap(ov);
     if (n == 0) return 0;
     Slot* sl = d.sl = acquire_slot_early();
     hipStream_t s = sl->stream;
     ChainTimer ev(s, "hsp chain timing");
-    rank_and_dp(hsps, n, group, T, costs, d, ev, st.chain);
+    rank_and_dp(hsps, n, group, T, costs, max_overlap, d, ev, st.chain);
     const uint32_t N = d.N;
 
     HspPeelArgs a;
@@ -314,12 +333,17 @@ extern "C" {
 
 size_t sa_chain_hsps(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p, sa_chain_member** members,
                      sa_chain_node** nodes, sa_chain_stats* stats) {
-    return chain_hsps(hsps, n, group, p, nullptr, members, nodes, stats);
+    return chain_hsps(hsps, n, group, p, nullptr, nullptr, members, nodes, stats);
 }
 
 size_t sa_chain_hsps_costs(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p,
                            const sa_chain_gap_costs* g, sa_chain_member** members, sa_chain_node** nodes, sa_chain_stats* stats) {
-    return chain_hsps(hsps, n, group, p, g, members, nodes, stats);
+    return chain_hsps(hsps, n, group, p, g, nullptr, members, nodes, stats);
+}
+
+size_t sa_chain_hsps_ovl(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p, const sa_chain_gap_costs* g,
+                         const sa_chain_overlap* ov, sa_chain_member** members, sa_chain_node** nodes, sa_chain_stats* stats) {
+    return chain_hsps(hsps, n, group, p, g, ov, members, nodes, stats);
 }
 
 void sa_free_chain(sa_chain_member* members, sa_chain_node* nodes) {
@@ -330,13 +354,19 @@ void sa_free_chain(sa_chain_member* members, sa_chain_node* nodes) {
 size_t sa_chain_hsps_all(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p, sa_chain_record** chains,
                          size_t* n_chains, sa_chain_all_member** members, sa_chain_node** nodes, uint32_t** chain_of,
                          sa_chain_all_stats* stats) {
-    return chain_hsps_all(hsps, n, group, p, nullptr, chains, n_chains, members, nodes, chain_of, stats);
+    return chain_hsps_all(hsps, n, group, p, nullptr, nullptr, chains, n_chains, members, nodes, chain_of, stats);
 }
 
 size_t sa_chain_hsps_all_costs(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p,
                                const sa_chain_gap_costs* g, sa_chain_record** chains, size_t* n_chains, sa_chain_all_member** members,
                                sa_chain_node** nodes, uint32_t** chain_of, sa_chain_all_stats* stats) {
-    return chain_hsps_all(hsps, n, group, p, g, chains, n_chains, members, nodes, chain_of, stats);
+    return chain_hsps_all(hsps, n, group, p, g, nullptr, chains, n_chains, members, nodes, chain_of, stats);
+}
+
+size_t sa_chain_hsps_all_ovl(const sa_segment_pair* hsps, size_t n, const uint32_t* group, const sa_chain_params* p,
+                             const sa_chain_gap_costs* g, const sa_chain_overlap* ov, sa_chain_record** chains, size_t* n_chains,
+                             sa_chain_all_member** members, sa_chain_node** nodes, uint32_t** chain_of, sa_chain_all_stats* stats) {
+    return chain_hsps_all(hsps, n, group, p, g, ov, chains, n_chains, members, nodes, chain_of, stats);
 }
 
 int sa_chain_gap_preset(const char* name, sa_chain_gap_costs* out) {

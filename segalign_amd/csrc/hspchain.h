@@ -26,6 +26,14 @@ struct HspChainPartial {  // the best candidate one earlier tile offers a node: 
     uint32_t rank, pad;
 };
 
+// What the overlap instances of the DP (hspovl.hip) know of a node beyond HspChainArgs, in rank order, both made by the
+// weight kernel: w = floor(65536 max(score, 0) / bases), below 2^47, and lim = min(len >> 1, max_overlap), the largest overlap the node
+// takes part in.  A separate struct, so that the kernel arguments of the plain instances stay what they were.
+struct HspOvlNodes {
+    const int64_t* w;
+    const uint32_t* lim;
+};
+
 // ---- rank ----
 // key[i] = query_start << 32 | len, idx[i] = i: the first (minor) stable sort.
 void launch_hspchain_key_minor(const sa_segment_pair* hsps, uint32_t n, uint64_t* key, uint32_t* idx, hipStream_t s);
@@ -44,6 +52,15 @@ void launch_hspchain_first(const uint32_t* gr, uint32_t n, uint32_t tile, uint32
 void launch_hspchain_cross(const HspChainArgs& a, uint32_t b, uint32_t c0, HspChainPartial* partial, const uint32_t* image, hipStream_t s);
 // Resolve: one workgroup reduces tile b's partials over c, settles the tile's own dependencies and writes its f and pred.
 void launch_hspchain_resolve(const HspChainArgs& a, uint32_t b, uint32_t c0, const HspChainPartial* partial, const uint32_t* image, hipStream_t s);
+
+// ---- the DP under an overlap allowance (hspovl.hip) ----
+// w[r], lim[r] of HspOvlNodes for every rank r < n from a.ln and a.sc: one division per node.
+void launch_hspovl_weight(const HspChainArgs& a, uint32_t max_overlap, int64_t* w, uint32_t* lim, hipStream_t s);
+// launch_hspchain_cross and launch_hspchain_resolve under the relation, gaps and charge of sa_chain_hsps_ovl: same grids, same partials.
+void launch_hspovl_cross(const HspChainArgs& a, const HspOvlNodes& o, uint32_t b, uint32_t c0, HspChainPartial* partial, const uint32_t* image,
+                         hipStream_t s);
+void launch_hspovl_resolve(const HspChainArgs& a, const HspOvlNodes& o, uint32_t b, uint32_t c0, const HspChainPartial* partial,
+                           const uint32_t* image, hipStream_t s);
 
 // ---- finish ----
 // gstart[g] = first rank of the g-th group, from the head flags and their exclusive scan.

@@ -20,7 +20,7 @@ constexpr uint32_t HSPCOST_SLOPE_LIMIT = 1u << 27;
 // The gap cost of a link with gaps dt, dq from an image, in LDS (hspchain.hip) or in global memory (netsubset.hip): the one lookup both
 // units use, so that a sub-chain is priced as its chain was.  For a pair that is no link (a negative gap) the value is arbitrary but
 // every step stays in range: the search clamps x into 32 bits, the distance past the break point is clamped at 0.
-__device__ __forceinline__ int64_t hspcost_gapcost(const uint32_t* img, int64_t dt, int64_t dq) {
+__host__ __device__ __forceinline__ int64_t hspcost_gapcost(const uint32_t* img, int64_t dt, int64_t dq) {
     const int64_t x = dt + dq;
     const uint32_t off = dt == 0 ? 0u : dq == 0 ? HSPCOST_POINTS : 2 * HSPCOST_POINTS;
     const uint32_t xc = ((uint64_t)x >> 32) ? 0xFFFFFFFFu : (uint32_t)x;  // pos < 2^32: the search gives the same row as with x

@@ -45,6 +45,7 @@ C_ABI_SYMBOLS = [
     "sa_gapped_extend", "sa_free_gapped", "sa_gapped_align", "sa_free_gapped_align", "sa_gapped_align_greedy",
     "sa_chain_hsps", "sa_free_chain", "sa_chain_hsps_all", "sa_free_chain_all",
     "sa_chain_hsps_costs", "sa_chain_hsps_all_costs", "sa_chain_gap_preset",
+    "sa_chain_hsps_ovl", "sa_chain_hsps_all_ovl", "sa_trim_chains", "sa_free_trim",
     "sa_stitch_chains", "sa_free_stitch",
     "sa_net_chains", "sa_free_net",
     "sa_net_subset", "sa_free_net_subset",
@@ -104,6 +105,23 @@ CHAIN_GAP_POINTS = 16
 class ChainGapCosts(C.Structure):  # sa_chain_gap_costs
     _fields_ = [("n", C.c_uint32), ("pad", C.c_uint32), ("pos", C.c_uint32 * CHAIN_GAP_POINTS), ("q_gap", C.c_int64 * CHAIN_GAP_POINTS),
                 ("t_gap", C.c_int64 * CHAIN_GAP_POINTS), ("both_gap", C.c_int64 * CHAIN_GAP_POINTS)]
+
+
+CHAIN_MAX_OVERLAP = 4096
+
+
+class ChainOverlap(C.Structure):  # sa_chain_overlap
+    _fields_ = [("max_overlap", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+TRIM_CHAIN_DTYPE = np.dtype([("score", "<i8"), ("trimmed_links", "<u4"), ("bases_cut", "<u4")])  # sa_trim_chain
+TRIM_LINK_DTYPE = np.dtype([("o", "<u4"), ("x", "<u4"), ("gap_r", "<u4"), ("gap_q", "<u4")])  # sa_trim_link
+TRIM_LINKS = 1
+
+
+class TrimStats(C.Structure):  # sa_trim_stats
+    _fields_ = [("chains", C.c_uint64), ("members", C.c_uint64), ("links", C.c_uint64), ("trimmed_links", C.c_uint64),
+                ("cut_members", C.c_uint64), ("bases_cut", C.c_uint64), ("kernel_ms", C.c_double)]
 
 
 class ChainStats(C.Structure):
@@ -380,6 +398,18 @@ def lib():
     L.sa_chain_hsps_all_costs.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(ChainParams), C.POINTER(ChainGapCosts),
                                           C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                           C.POINTER(C.c_void_p), C.POINTER(ChainAllStats)]
+    L.sa_chain_hsps_ovl.restype = C.c_size_t
+    L.sa_chain_hsps_ovl.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(ChainParams), C.POINTER(ChainGapCosts),
+                                    C.POINTER(ChainOverlap), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(ChainStats)]
+    L.sa_chain_hsps_all_ovl.restype = C.c_size_t
+    L.sa_chain_hsps_all_ovl.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(ChainParams), C.POINTER(ChainGapCosts),
+                                        C.POINTER(ChainOverlap), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(ChainAllStats)]
+    L.sa_trim_chains.restype = C.c_size_t
+    L.sa_trim_chains.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(ChainParams),
+                                 C.POINTER(ChainGapCosts), C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                 C.POINTER(C.c_size_t), C.POINTER(TrimStats)]
+    L.sa_free_trim.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.sa_chain_gap_preset.restype = C.c_int
     L.sa_chain_gap_preset.argtypes = [C.c_char_p, C.POINTER(ChainGapCosts)]
     L.sa_stitch_chains.restype = C.c_size_t
@@ -669,6 +699,14 @@ def _chain_input(hsps, groups, diag_pen, anti_pen, max_gap, min_score):
     return h, g, ChainParams(int(diag_pen), int(anti_pen), int(max_gap), 0, int(min_score))
 
 
+def _chain_overlap(max_overlap):
+    """max_overlap as an int in 0 .. CHAIN_MAX_OVERLAP; ValueError otherwise (the library would end the process)."""
+    mo = int(max_overlap)
+    if not 0 <= mo <= CHAIN_MAX_OVERLAP:
+        raise ValueError("max_overlap: %d is not in 0 .. %d" % (mo, CHAIN_MAX_OVERLAP))
+    return mo
+
+
 def _chain_take(ptr, count, dtype):
     """A copy of count records at a malloc-ed result pointer."""
     dtype = np.dtype(dtype)
@@ -729,14 +767,21 @@ def parse_linear_gap(text):
     return {"pos": want["position"], "q_gap": want["qGap"], "t_gap": want["tGap"], "both_gap": want["bothGap"]}
 
 
-def ChainHsps(hsps, groups=None, diag_pen=0, anti_pen=0, max_gap=0, min_score=0, nodes=False, gap_costs=None):
+def ChainHsps(hsps, groups=None, diag_pen=0, anti_pen=0, max_gap=0, min_score=0, nodes=False, gap_costs=None, max_overlap=0):
     """The best collinear chain of every group of HSPs (sa_chain_hsps; contract in include/segalign_amd.h).
     hsps: SEG_DTYPE records; groups: one uint32 per HSP (None: all in group 0).  -> (CHAIN_MEMBER_DTYPE members, stats dict), or with
     nodes=True (members, CHAIN_NODE_DTYPE nodes in input order, stats dict).  gap_costs: what chain_gap_costs takes, for a link's
-    piecewise-linear gap cost on top of the linear terms (sa_chain_hsps_costs); None: none.  Needs InitializeInterface only."""
+    piecewise-linear gap cost on top of the linear terms (sa_chain_hsps_costs); None: none.  max_overlap: the most bases
+    two linked HSPs may share on an axis, 0 .. CHAIN_MAX_OVERLAP (sa_chain_hsps_ovl); 0 calls the entries above as
+    before.  Needs InitializeInterface only."""
     h, g, p = _chain_input(hsps, groups, diag_pen, anti_pen, max_gap, min_score)
+    max_overlap = _chain_overlap(max_overlap)
     mem, nod, st = C.c_void_p(), C.c_void_p(), ChainStats()
-    if gap_costs is not None:
+    if max_overlap:
+        m = lib().sa_chain_hsps_ovl(h.ctypes.data if h.size else None, h.size, g.ctypes.data if g is not None and g.size else None,
+                                    C.byref(p), C.byref(chain_gap_costs(gap_costs)) if gap_costs is not None else None,
+                                    C.byref(ChainOverlap(max_overlap, 0)), C.byref(mem), C.byref(nod) if nodes else None, C.byref(st))
+    elif gap_costs is not None:
         m = lib().sa_chain_hsps_costs(h.ctypes.data if h.size else None, h.size, g.ctypes.data if g is not None and g.size else None,
                                       C.byref(p), C.byref(chain_gap_costs(gap_costs)), C.byref(mem), C.byref(nod) if nodes else None,
                                       C.byref(st))
@@ -748,14 +793,21 @@ def ChainHsps(hsps, groups=None, diag_pen=0, anti_pen=0, max_gap=0, min_score=0,
     return (res_m, res_n, _flat(st)) if nodes else (res_m, _flat(st))
 
 
-def ChainHspsAll(hsps, groups=None, diag_pen=0, anti_pen=0, max_gap=0, min_score=0, nodes=False, gap_costs=None):
+def ChainHspsAll(hsps, groups=None, diag_pen=0, anti_pen=0, max_gap=0, min_score=0, nodes=False, gap_costs=None, max_overlap=0):
     """All collinear chains of every group of HSPs, peeled best first (sa_chain_hsps_all; contract in include/segalign_amd.h,
     DESIGN.md 16).  Arguments as ChainHsps.  -> (CHAIN_RECORD_DTYPE chains, CHAIN_ALL_MEMBER_DTYPE members, uint32 chain_of in input
     order (CHAIN_NONE: the HSP's chain scores below min_score), stats dict); with nodes=True the CHAIN_NODE_DTYPE nodes come before
-    chain_of.  gap_costs as for ChainHsps (sa_chain_hsps_all_costs).  Needs InitializeInterface only."""
+    chain_of.  gap_costs as for ChainHsps (sa_chain_hsps_all_costs), max_overlap too (sa_chain_hsps_all_ovl).  Needs
+    InitializeInterface only."""
     h, g, p = _chain_input(hsps, groups, diag_pen, anti_pen, max_gap, min_score)
     ch, mem, nod, cof, st, nc = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), ChainAllStats(), C.c_size_t(0)
-    if gap_costs is not None:
+    max_overlap = _chain_overlap(max_overlap)
+    if max_overlap:
+        m = lib().sa_chain_hsps_all_ovl(h.ctypes.data if h.size else None, h.size, g.ctypes.data if g is not None and g.size else None,
+                                        C.byref(p), C.byref(chain_gap_costs(gap_costs)) if gap_costs is not None else None,
+                                        C.byref(ChainOverlap(max_overlap, 0)), C.byref(ch), C.byref(nc), C.byref(mem),
+                                        C.byref(nod) if nodes else None, C.byref(cof), C.byref(st))
+    elif gap_costs is not None:
         m = lib().sa_chain_hsps_all_costs(h.ctypes.data if h.size else None, h.size, g.ctypes.data if g is not None and g.size else None,
                                           C.byref(p), C.byref(chain_gap_costs(gap_costs)), C.byref(ch), C.byref(nc), C.byref(mem),
                                           C.byref(nod) if nodes else None, C.byref(cof), C.byref(st))
@@ -767,6 +819,27 @@ def ChainHspsAll(hsps, groups=None, diag_pen=0, anti_pen=0, max_gap=0, min_score
     res_n, res_o = _chain_take(nod, h.size, CHAIN_NODE_DTYPE), _chain_take(cof, h.size, np.uint32)
     lib().sa_free_chain_all(ch, mem, nod, cof)
     return (res_c, res_m, res_n, res_o, _flat(st)) if nodes else (res_c, res_m, res_o, _flat(st))
+
+
+def TrimChains(hsps, members, first, rev, buffer=0, diag_pen=0, anti_pen=0, gap_costs=None, links=False):
+    """Cuts the overlaps between consecutive members of chains at the best crossover (sa_trim_chains; contract in
+    include/segalign_amd.h).  hsps: SEG_DTYPE records; members, first: the chains as chain_csr gives them; rev, buffer:
+    the resident query strand and buffer; the penalties and gap_costs the chains were made under.  -> (SEG_DTYPE trimmed HSPs, one per
+    member entry: go on with members = arange(M) and first unchanged; TRIM_CHAIN_DTYPE chains; stats dict), with links=True the
+    TRIM_LINK_DTYPE links before the stats."""
+    h = np.ascontiguousarray(hsps, dtype=SEG_DTYPE)
+    mem, fst = np.ascontiguousarray(members, dtype=np.uint32), np.ascontiguousarray(first, dtype=np.uint32)
+    if fst.size == 0 or (fst.size and int(fst[-1]) != mem.size):
+        raise ValueError("first: one more entry than chains, the last one the number of members")
+    p = ChainParams(int(diag_pen), int(anti_pen), 0, 0, 0)
+    out, ch, lk, nl, st = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t(0), TrimStats()
+    m = lib().sa_trim_chains(h.ctypes.data if h.size else None, h.size, mem.ctypes.data if mem.size else None, fst.ctypes.data, fst.size - 1,
+                             int(bool(rev)), int(buffer), C.byref(p), C.byref(chain_gap_costs(gap_costs)) if gap_costs is not None else None,
+                             TRIM_LINKS if links else 0, C.byref(out), C.byref(ch), C.byref(lk), C.byref(nl), C.byref(st))
+    res_h, res_c = _chain_take(out, m, SEG_DTYPE), _chain_take(ch, fst.size - 1 if m else 0, TRIM_CHAIN_DTYPE)
+    res_l = _chain_take(lk, nl.value, TRIM_LINK_DTYPE)
+    lib().sa_free_trim(out, ch, lk)
+    return (res_h, res_c, res_l, _flat(st)) if links else (res_h, res_c, _flat(st))
 
 
 def chain_csr(members):

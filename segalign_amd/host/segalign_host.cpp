@@ -51,6 +51,8 @@ struct Config {  // src/graph.h:32-76 with the defaults of src/main.cpp:61-124
     long long chain_min = 0;  // --gpu_chain_min=N: sa_chain_params.min_score of --gpu_chain_all
     bool chain_costs_set = false;  // --gpu_chain_costs=loose|medium|FILE (with --gpu_chain or --gpu_chain_all): a piecewise-linear gap cost per link
     sa_chain_gap_costs chain_costs;  // (sa_chain_hsps_costs / sa_chain_hsps_all_costs)
+    uint32_t chain_overlap = 0;  // --gpu_chain_overlap[=N] (with --gpu_chain or --gpu_chain_all): chain members may share up to N bases
+                                 // (sa_chain_hsps_ovl / sa_chain_hsps_all_ovl) and the chains are trimmed (sa_trim_chains); 0: off
     bool gpu_stitch = false;  // --gpu_stitch[=max_link] (with --gpu_chain or --gpu_chain_all): a .stitched.maf file next to every .chain / .chains file (sa_stitch_chains)
     uint32_t stitch_max_link = 0;  // sa_stitch_params.max_link; 0: the engine's default
     bool stitch_min_set = false;
@@ -333,12 +335,16 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
             std::vector<int64_t> cscore;              // with --gpu_net: every kept chain's score and the target record of its pair
             std::vector<uint32_t> ctarget;
             std::vector<uint32_t> cquery;             // with --gpu_net_class: the query record of its pair
+            const sa_chain_gap_costs* costs = cfg.chain_costs_set ? &cfg.chain_costs : nullptr;
+            const sa_chain_overlap ov = {cfg.chain_overlap, 0};
+            std::vector<sa_chain_record> crec;        // with --gpu_chain_all: the kept chains' records
             if (cfg.gpu_chain) {
                 sa_chain_member* mem = nullptr;
-                const size_t nm = cfg.chain_costs_set ? sa_chain_hsps_costs(v.data(), v.size(), group.data(), &cp, &cfg.chain_costs, &mem, nullptr, nullptr)
+                const size_t nm = cfg.chain_overlap ? sa_chain_hsps_ovl(v.data(), v.size(), group.data(), &cp, costs, &ov, &mem, nullptr, nullptr)
+                                : cfg.chain_costs_set ? sa_chain_hsps_costs(v.data(), v.size(), group.data(), &cp, &cfg.chain_costs, &mem, nullptr, nullptr)
                                                       : sa_chain_hsps(v.data(), v.size(), group.data(), &cp, &mem, nullptr, nullptr);
                 idx.resize(nm);
-                for (size_t k = 0; k < nm; k++) { emit(v[mem[k].hsp_index]); idx[k] = mem[k].hsp_index; }  // the order sa_chain_hsps returns, on both strands
+                for (size_t k = 0; k < nm; k++) idx[k] = mem[k].hsp_index;  // the order sa_chain_hsps returns, on both strands
                 for (size_t k = 1; k <= nm; k++)
                     if (k == nm || mem[k].group != mem[k - 1].group) cfirst.push_back((uint32_t)k);  // one chain per group
                 sa_free_chain(mem, nullptr);
@@ -346,22 +352,48 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
                 sa_chain_record* ch = nullptr;
                 sa_chain_all_member* mem = nullptr;
                 size_t nc = 0;
-                const size_t nm = cfg.chain_costs_set
+                const size_t nm = cfg.chain_overlap
+                    ? sa_chain_hsps_all_ovl(v.data(), v.size(), group.data(), &cp, costs, &ov, &ch, &nc, &mem, nullptr, nullptr, nullptr)
+                    : cfg.chain_costs_set
                     ? sa_chain_hsps_all_costs(v.data(), v.size(), group.data(), &cp, &cfg.chain_costs, &ch, &nc, &mem, nullptr, nullptr, nullptr)
                     : sa_chain_hsps_all(v.data(), v.size(), group.data(), &cp, &ch, &nc, &mem, nullptr, nullptr, nullptr);
                 idx.resize(nm);
-                for (size_t c = 0; c < nc; c++) {  // the order sa_chain_hsps_all returns, on both strands
-                    fprintf(f, "#chain %zu group=%u score=%lld members=%u joined=%d\n", c, ch[c].group, (long long)ch[c].score, ch[c].n_members,
-                            ch[c].joined >= 0 ? 1 : 0);
-                    for (size_t k = ch[c].first_member; k < (size_t)ch[c].first_member + ch[c].n_members; k++) { emit(v[mem[k].hsp_index]); idx[k] = mem[k].hsp_index; }
+                crec.assign(ch, ch + nc);
+                for (size_t c = 0; c < nc; c++) {
+                    for (size_t k = ch[c].first_member; k < (size_t)ch[c].first_member + ch[c].n_members; k++) idx[k] = mem[k].hsp_index;
                     cfirst.push_back(ch[c].first_member + ch[c].n_members);  // the chains' members follow one another
-                    if (cfg.gpu_net) {
-                        cscore.push_back(ch[c].score);
-                        ctarget.push_back((uint32_t)(pairs[ch[c].group] >> 32));
-                        cquery.push_back((uint32_t)pairs[ch[c].group]);
-                    }
                 }
                 sa_free_chain_all(ch, mem, nullptr, nullptr);
+            }
+            // with --gpu_chain_overlap the members may overlap: cut every overlap at the best crossover.  From here on the
+            // chains' HSP vector is the trimmed one, one entry per member, and the chains' scores are the exact ones
+            std::vector<sa_segment_pair> trimmed;
+            std::vector<uint32_t> untrimmed_idx;  // the members' indices in v
+            if (cfg.chain_overlap) {
+                sa_segment_pair* th = nullptr;
+                sa_trim_chain* tc = nullptr;
+                const size_t tm = sa_trim_chains(v.data(), v.size(), idx.data(), cfirst.data(), cfirst.size() - 1, rev, buffer, &cp, costs, 0, &th, &tc,
+                                                 nullptr, nullptr, nullptr);
+                trimmed.assign(th, th + tm);
+                for (size_t c = 0; c < crec.size(); c++) crec[c].score = tc[c].score;
+                sa_free_trim(th, tc, nullptr);
+                untrimmed_idx = idx;
+                for (size_t k = 0; k < idx.size(); k++) idx[k] = (uint32_t)k;
+            }
+            const std::vector<sa_segment_pair>& cv = cfg.chain_overlap ? trimmed : v;  // what idx indexes
+            if (cfg.gpu_chain) {
+                for (size_t k = 0; k < idx.size(); k++) emit(cv[idx[k]]);
+            } else {
+                for (size_t c = 0; c < crec.size(); c++) {  // the order sa_chain_hsps_all returns, on both strands
+                    fprintf(f, "#chain %zu group=%u score=%lld members=%u joined=%d\n", c, crec[c].group, (long long)crec[c].score, crec[c].n_members,
+                            crec[c].joined >= 0 ? 1 : 0);
+                    for (size_t k = crec[c].first_member; k < (size_t)crec[c].first_member + crec[c].n_members; k++) emit(cv[idx[k]]);
+                    if (cfg.gpu_net) {
+                        cscore.push_back(crec[c].score);
+                        ctarget.push_back((uint32_t)(pairs[crec[c].group] >> 32));
+                        cquery.push_back((uint32_t)pairs[crec[c].group]);
+                    }
+                }
             }
             fclose(f);
             // every chain of a CSR as one alignment through its members, in --gpu_maf's block layout, into the file sname
@@ -397,12 +429,12 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
                 fclose(sf);
                 sa_free_stitch(sr, sops, nullptr);
             };
-            if (cfg.gpu_stitch) write_stitched(base + ".stitched.maf", v.data(), v.size(), idx.data(), cfirst.data(), cfirst.size() - 1);
+            if (cfg.gpu_stitch) write_stitched(base + ".stitched.maf", cv.data(), cv.size(), idx.data(), cfirst.data(), cfirst.size() - 1);
             if (cfg.gpu_net) {  // which chain to believe where: the kept chains of every target record netted on the target axis
                 std::vector<uint32_t> bs(idx.size()), be(idx.size());  // a member is one block, in block coordinates
                 for (size_t k = 0; k < idx.size(); k++) {
-                    bs[k] = v[idx[k]].ref_start;
-                    be[k] = v[idx[k]].ref_start + v[idx[k]].len + 1;
+                    bs[k] = cv[idx[k]].ref_start;
+                    be[k] = cv[idx[k]].ref_start + cv[idx[k]].len + 1;
                 }
                 sa_net_params np = {cfg.net_space, cfg.net_fill};
                 sa_net_fill* nf = nullptr;
@@ -414,8 +446,8 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
                 if (cfg.gpu_net_class) {
                     std::vector<uint32_t> obs(idx.size()), obe(idx.size());
                     for (size_t k = 0; k < idx.size(); k++) {
-                        obs[k] = v[idx[k]].query_start;
-                        obe[k] = v[idx[k]].query_start + v[idx[k]].len + 1;
+                        obs[k] = cv[idx[k]].query_start;
+                        obe[k] = cv[idx[k]].query_start + cv[idx[k]].len + 1;
                     }
                     sa_net_classify(cfirst.data(), bs.data(), be.data(), obs.data(), obe.data(), cquery.data(), nullptr, cfirst.size() - 1, nf, nn,
                                     cfg.net_syn ? &cfg.net_syn_p : nullptr, cfg.net_syn ? SA_NETCLASS_FILTER : 0, &ncl, nullptr);
@@ -436,8 +468,8 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
                     }
                     // an HSP is ungapped: a clip on the target shifts the query by the same amount
                     const uint32_t k0 = x.first_block, k1 = x.first_block + x.n_blocks - 1;
-                    const size_t q0 = (size_t)v[idx[k0]].query_start + (x.start - bs[k0]) + q_block_start;
-                    const size_t q1 = (size_t)v[idx[k1]].query_start + (x.end - bs[k1]) + q_block_start;
+                    const size_t q0 = (size_t)cv[idx[k0]].query_start + (x.start - bs[k0]) + q_block_start;
+                    const size_t q1 = (size_t)cv[idx[k1]].query_start + (x.end - bs[k1]) + q_block_start;
                     const size_t qi = chr_of(qs, q0);
                     fprintf(nfp, "%*sfill %zu %u %s %c %zu %zu chain=%u score=%lld ali=%u\n", (int)x.depth, "", x.start + r_block_start - R.chr_start[ri],
                             x.end - x.start, qn[qi].c_str(), rev ? '-' : '+', q0 - qs[qi], q1 - q0, x.chain, (long long)x.score, x.ali);
@@ -472,7 +504,7 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
                     sa_segment_pair* oh = nullptr;
                     sa_subset_chain* sc = nullptr;
                     size_t n_oh = 0;
-                    const size_t nsc = sa_net_subset(v.data(), v.size(), idx.data(), cfirst.data(), cfirst.size() - 1, sub_fills, n_sub_fills, 0, rev, buffer, &cp,
+                    const size_t nsc = sa_net_subset(cv.data(), cv.size(), idx.data(), cfirst.data(), cfirst.size() - 1, sub_fills, n_sub_fills, 0, rev, buffer, &cp,
                                                      cfg.chain_costs_set ? &cfg.chain_costs : nullptr, SA_SUBSET_SPLIT, &oh, &n_oh, &sc, nullptr);
                     std::string sname = base + ".net.chains";
                     f = fopen((cfg.outdir + "/" + sname).c_str(), "w");
@@ -546,9 +578,15 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
                 }
                 sa_free_net(nf);
             }
-            std::sort(idx.begin(), idx.end());  // an HSP is a member of one chain at most: no duplicates
             kept.reserve(idx.size());
-            for (uint32_t i : idx) kept.push_back(v[i]);
+            if (cfg.chain_overlap) {  // the trimmed members in the order of their HSPs within v
+                std::vector<uint32_t> ord(idx);
+                std::sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return untrimmed_idx[x] < untrimmed_idx[y]; });
+                for (uint32_t k : ord) kept.push_back(trimmed[k]);
+            } else {
+                std::sort(idx.begin(), idx.end());  // an HSP is a member of one chain at most: no duplicates
+                for (uint32_t i : idx) kept.push_back(v[i]);
+            }
         }
         const std::vector<sa_segment_pair>& anchors = (cfg.gpu_chain || cfg.gpu_chain_all) ? kept : v;  // what the gapped entries extend
         if (cfg.gpu_gapped) {  // the gapped extension of the same HSPs on the device: [start, end) extents printed like the segments
@@ -657,6 +695,10 @@ static void usage() {
             "  --gpu_chain_costs=loose|medium|FILE (with --gpu_chain or --gpu_chain_all: a link also pays a piecewise-linear gap cost, in the\n"
             "      spirit of axtChain -linearGap: its two preset tables, or a FILE in its layout with at most 16 break points: lines\n"
             "      'tableSize N', 'smallSize N' (ignored), 'position ...', 'qGap ...', 'tGap ...', 'bothGap ...')\n"
+            "  --gpu_chain_overlap[=N] (with --gpu_chain or --gpu_chain_all: two chained HSPs may share up to N bases, default 64, at most 4096 and\n"
+            "      less than half of the shorter, on either sequence, as HSPs on the two sides of an indel do; every overlap is then cut where the\n"
+            "      two together score best, so the .chain / .chains files hold the trimmed members with their exact scores and the exact chain\n"
+            "      scores, and every later stage of the run gets those)\n"
             "  --gpu_stitch[=max_link] (with --gpu_chain or --gpu_chain_all: a .stitched.maf file next to each .chain / .chains file with every\n"
             "      chain as one alignment through all its members, the stretch between two members aligned globally with --gap=O,E; a chain\n"
             "      is cut where a side of that stretch exceeds max_link (default and at most 2048) or holds a record boundary)\n"
@@ -792,6 +834,13 @@ int main(int argc, char** argv) {
             if (endp == v.c_str() || *endp || gap < 0 || gap > 0xffffffffll) { fprintf(stderr, "bad --gpu_chain_gap=%s (0 .. 4294967295; 0: unlimited)\n", v.c_str()); return 1; }
             cfg.chain_gap = (uint32_t)gap;
         }
+        else if (!strcmp(a, "--gpu_chain_overlap")) cfg.chain_overlap = 64;
+        else if (opt(a, "--gpu_chain_overlap", v)) {
+            char* endp = nullptr;
+            const long long n = strtoll(v.c_str(), &endp, 10);
+            if (endp == v.c_str() || *endp || n < 1 || n > SA_CHAIN_MAX_OVERLAP) { fprintf(stderr, "bad --gpu_chain_overlap=%s (1 .. %d)\n", v.c_str(), SA_CHAIN_MAX_OVERLAP); return 1; }
+            cfg.chain_overlap = (uint32_t)n;
+        }
         else if (opt(a, "--gpu_chain_costs", v)) {
             std::string err;
             if (sa_chain_gap_preset(v.c_str(), &cfg.chain_costs) != 0 && !read_linear_gap(v, cfg.chain_costs, err)) {
@@ -872,6 +921,7 @@ int main(int argc, char** argv) {
     if (cfg.gpu_chain && cfg.gpu_chain_all) { fprintf(stderr, "--gpu_chain and --gpu_chain_all exclude each other\n"); return 1; }
     if (cfg.chain_min_set && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_chain_min needs --gpu_chain_all\n"); return 1; }
     if (cfg.chain_costs_set && !cfg.gpu_chain && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_chain_costs needs --gpu_chain or --gpu_chain_all\n"); return 1; }
+    if (cfg.chain_overlap && !cfg.gpu_chain && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_chain_overlap needs --gpu_chain or --gpu_chain_all\n"); return 1; }
     if (cfg.gpu_stitch && !cfg.gpu_chain && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_stitch needs --gpu_chain or --gpu_chain_all\n"); return 1; }
     if (cfg.stitch_min_set && !cfg.gpu_stitch) { fprintf(stderr, "--gpu_stitch_min needs --gpu_stitch\n"); return 1; }
     if (cfg.gpu_net && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_net needs --gpu_chain_all\n"); return 1; }

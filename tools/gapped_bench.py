@@ -19,6 +19,13 @@ table (FILE: axtChain's linearGap layout) on top of --chain-pen, in runs that al
 chain kernel ms and pair evaluations per second of the table runs beside the linear ones, every run's kernel ms, their ratio, and the
 members and score under the table.  f, pred and the members are checked against tests/hsp_chain_gap_model.py once per run.
 
+With --chain-overlap N (with --chain) the same HSPs also go through sa_chain_hsps_ovl under an allowance of N bases, on
+top of --chain-pen and --chain-costs, in runs that alternate with the plain ones (the table's where one is given, the linear ones
+otherwise): the line then adds the kernel ms of both, every run's, their ratio, and members and score with and without the allowance.
+f, pred and the members are checked against tests/hsp_chain_overlap_model.py once per run.  The chain is then trimmed (sa_trim_chains):
+the line adds trim ms (the least of the runs), the links trimmed, the members cut and the exact score, checked against
+tests/chain_trim_model.py once per run.  The later stages (--chain-all, --stitch, --net ...) go on from the plain chains.
+
 With --chain-all [--chain-min N] (which implies --chain) the HSPs also go through sa_chain_hsps_all: the line then adds
 the chains before min_score, the chains, joined chains and members kept, the doubling rounds, peel ms beside the DP's kernel ms, and
 the gapped times on the kept chains' members beside those on the best chain and on all HSPs.  The chains, members and chain_of are
@@ -51,7 +58,7 @@ launches (the sort's and the running maximum's come on top).  The records, hits 
 sub-chains, under both flags, are checked against the model (tests/lift_model.py) once per run.
 
   python tools/gapped_bench.py [--workloads standin,lumpy] [--repeat 3] [--align] [--greedy] [--batches 1024,2048,...]
-                               [--pieces N] [--max-extent M] [--chain] [--chain-pen D,A] [--chain-costs T] [--chain-all] [--chain-min N] [--stitch] [--stitch-max-link N]
+                               [--pieces N] [--max-extent M] [--chain] [--chain-pen D,A] [--chain-costs T] [--chain-overlap N] [--chain-all] [--chain-min N] [--stitch] [--stitch-max-link N]
                                [--net] [--net-space N] [--net-fill N] [--net-subset] [--net-class] [--net-class-filter S,T,Z,A,F] [--lift[=N]]
 """
 import argparse
@@ -411,22 +418,66 @@ def chain_costs_fields(hsps, pen, costs, runs, linear_ms):
             "chain_costs_model_checked": True, "chain_costs_model_s": round(model_s, 1)}
 
 
-def chain_fields(hsps, repeat, pen, align, greedy, all_min=None, stitch=None, net=None, costs=None):
+def chain_overlap_fields(hsps, pen, costs, overlap, runs, plain_runs):
+    """The runs of sa_chain_hsps_ovl that chain_fields interleaved with the plain ones (under the table where there is one), checked
+    against the model."""
+    import hsp_chain_overlap_model as OM
+    members, nodes, st = min(runs, key=lambda r: r[2]["kernel_ms"])
+    plain_m, _, plain_st = min(plain_runs, key=lambda r: r[2]["kernel_ms"])
+    t0 = time.perf_counter()
+    f, pred, want = OM.chain_rows(hsps, None, diag_pen=pen[0], anti_pen=pen[1], gap_costs=chain_costs_table(costs) if costs else None,
+                                  max_overlap=overlap)
+    model_s = time.perf_counter() - t0
+    if not (np.array_equal(nodes["f"], f) and np.array_equal(nodes["pred"], pred) and np.array_equal(members, want)):
+        raise SystemExit("sa_chain_hsps_ovl differs from the model")
+    idx = members["hsp_index"]
+    re, qe = hsps["ref_start"].astype(np.int64) + hsps["len"] + 1, hsps["query_start"].astype(np.int64) + hsps["len"] + 1
+    o = np.maximum(0, np.maximum(re[idx[:-1]] - hsps["ref_start"][idx[1:]], qe[idx[:-1]] - hsps["query_start"][idx[1:]])) if idx.size > 1 else np.zeros(0)
+    ms, plain_ms = st["kernel_ms"], plain_st["kernel_ms"]
+    import chain_trim_model as TM
+    mem, first = E.chain_csr(members)
+    table = chain_costs_table(costs) if costs else None
+    trims = [E.TrimChains(hsps, mem, first, False, 0, diag_pen=pen[0], anti_pen=pen[1], gap_costs=table, links=True) for _ in runs]
+    t_out, t_ch, t_links, t_st = min(trims, key=lambda r: r[3]["kernel_ms"])
+    w_out, w_ch, w_links = TM.trim(E.copy_ref_codes(), E.copy_query_codes(0, False), SUB, hsps, mem, first, diag_pen=pen[0], anti_pen=pen[1],
+                                   gap_costs=table)
+    if not (all(np.array_equal(t_out[k], w_out[k]) for k in w_out.dtype.names) and all(np.array_equal(t_ch[k], w_ch[k]) for k in w_ch.dtype.names)
+            and all(np.array_equal(t_links[k], w_links[k]) for k in w_links.dtype.names)):
+        raise SystemExit("sa_trim_chains differs from the model")
+    trim = {"trim_ms": round(t_st["kernel_ms"], 3), "trim_runs_ms": [round(r[3]["kernel_ms"], 3) for r in trims],
+            "trim_links": int(t_st["trimmed_links"]), "trim_cut_members": int(t_st["cut_members"]), "trim_bases_cut": int(t_st["bases_cut"]),
+            "trim_exact_score": int(t_ch["score"][0]) if t_ch.size else None, "trim_model_checked": True}
+    return {**trim, "chain_overlap": int(overlap), "chain_overlap_members": int(st["members"]), "chain_overlap_score": int(members["f"][-1]) if members.size else None,
+            "chain_overlap_links_overlapping": int((o > 0).sum()), "chain_overlap_largest": int(o.max()) if o.size else 0,
+            "chain_overlap_plain_members": int(plain_st["members"]), "chain_overlap_plain_score": int(plain_m["f"][-1]) if plain_m.size else None,
+            "chain_overlap_kernel_ms": round(ms, 3), "chain_overlap_plain_kernel_ms": round(plain_ms, 3),
+            "chain_overlap_runs_ms": [round(r[2]["kernel_ms"], 3) for r in runs], "chain_overlap_plain_runs_ms": [round(r[2]["kernel_ms"], 3) for r in plain_runs],
+            "chain_overlap_median_ms": round(float(np.median([r[2]["kernel_ms"] for r in runs])), 3),
+            "chain_overlap_plain_median_ms": round(float(np.median([r[2]["kernel_ms"] for r in plain_runs])), 3),
+            "chain_overlap_over_plain": round(float(np.median([r[2]["kernel_ms"] for r in runs]) / np.median([r[2]["kernel_ms"] for r in plain_runs])), 3),
+            "chain_overlap_model_checked": True, "chain_overlap_model_s": round(model_s, 1)}
+
+
+def chain_fields(hsps, repeat, pen, align, greedy, all_min=None, stitch=None, net=None, costs=None, overlap=0):
     """sa_chain_hsps on the HSPs as one group, checked against the numpy model, and the gapped entries on the chain's members; with
-    all_min also chain_all_fields, with costs also chain_costs_fields (its runs alternate with the linear ones)."""
+    all_min also chain_all_fields, with costs also chain_costs_fields (its runs alternate with the linear ones), with overlap also
+    chain_overlap_fields (its runs alternate with the plain ones)."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import hsp_chain_model as M
-    best, cost_runs, linear_ms = None, [], []
+    best, cost_runs, linear_ms, linear_runs, overlap_runs = None, [], [], [], []
     table = E.chain_gap_costs(chain_costs_table(costs)) if costs else None
     for _ in range(repeat):
         t0 = time.perf_counter()
         r = E.ChainHsps(hsps, None, diag_pen=pen[0], anti_pen=pen[1], nodes=True)
         wall = (time.perf_counter() - t0) * 1e3
         linear_ms.append(r[2]["kernel_ms"])
+        linear_runs.append(r)
         if best is None or r[2]["kernel_ms"] < best[0][2]["kernel_ms"]:
             best = (r, wall)
         if table is not None:
             cost_runs.append(E.ChainHsps(hsps, None, diag_pen=pen[0], anti_pen=pen[1], nodes=True, gap_costs=table))
+        if overlap:
+            overlap_runs.append(E.ChainHsps(hsps, None, diag_pen=pen[0], anti_pen=pen[1], nodes=True, gap_costs=table, max_overlap=overlap))
     (members, nodes, st), wall = best
     t0 = time.perf_counter()
     f, pred, want = M.chain(hsps, None, diag_pen=pen[0], anti_pen=pen[1])
@@ -441,13 +492,16 @@ def chain_fields(hsps, repeat, pen, align, greedy, all_min=None, stitch=None, ne
            "chain_model_checked": True, "chain_model_s": round(model_s, 1)}
     if costs:
         out.update(chain_costs_fields(hsps, pen, costs, cost_runs, linear_ms))
+    if overlap:
+        out.update(chain_overlap_fields(hsps, pen, costs, overlap, overlap_runs, cost_runs if costs else linear_runs))
     out.update(kept_fields(kept, repeat, align, greedy, "kept_"))
     if all_min is not None:
         out.update(chain_all_fields(hsps, repeat, pen, all_min, (f, pred), align, greedy, stitch, net))
     return out
 
 
-def run(name, repeat, align=False, greedy=False, with_sel=True, pieces=0, chain=None, chain_all_min=None, stitch=None, net=None, chain_costs=None):
+def run(name, repeat, align=False, greedy=False, with_sel=True, pieces=0, chain=None, chain_all_min=None, stitch=None, net=None, chain_costs=None,
+        chain_overlap=0):
     t, q = workload(name)
     if greedy or pieces:
         E.set_option("debug", 1)  # sa_gapped_align_greedy then prints its edge count, the continuation its pieces
@@ -495,7 +549,7 @@ def run(name, repeat, align=False, greedy=False, with_sel=True, pieces=0, chain=
     if greedy:
         extra.update(greedy_fields(hsps, repeat, with_sel))
     if chain is not None:
-        extra.update(chain_fields(hsps, repeat, chain, align, greedy, chain_all_min, stitch, net, chain_costs))
+        extra.update(chain_fields(hsps, repeat, chain, align, greedy, chain_all_min, stitch, net, chain_costs, chain_overlap))
     E.ShutdownProcessor()
     if greedy or pieces:
         E.reset_option("debug")
@@ -520,6 +574,7 @@ def main():
     ap.add_argument("--chain", action="store_true", help="also chain the HSPs (sa_chain_hsps) and time the gapped entries on the chain's members")
     ap.add_argument("--chain-pen", default="0,0", help="with --chain: diag_pen,anti_pen")
     ap.add_argument("--chain-costs", default="", help="with --chain: also chain under this gap-cost table (loose, medium or a linearGap file)")
+    ap.add_argument("--chain-overlap", type=int, default=0, help="with --chain: also chain under this overlap allowance (1 .. 4096 bases)")
     ap.add_argument("--chain-all", action="store_true", help="also peel the HSPs into all chains (sa_chain_hsps_all); implies --chain")
     ap.add_argument("--chain-min", type=int, default=0, help="with --chain-all: min_score")
     ap.add_argument("--stitch", action="store_true", help="also stitch the kept chains (sa_stitch_chains); implies --chain-all")
@@ -545,13 +600,17 @@ def main():
     chain = tuple(int(x) for x in a.chain_pen.split(",")) if a.chain or a.chain_all else None
     if a.chain_costs and chain is None:
         ap.error("--chain-costs needs --chain")
+    if not 0 <= a.chain_overlap <= 4096:
+        ap.error("--chain-overlap takes 0 .. 4096 (0: off)")
+    if a.chain_overlap and chain is None:
+        ap.error("--chain-overlap needs --chain")
     if a.max_extent:
         KW["max_extent"] = a.max_extent
     for name in a.workloads.split(","):
         if not a.batches:
             print(json.dumps(run(name, a.repeat, a.align, a.greedy, pieces=a.pieces, chain=chain, chain_all_min=a.chain_min if a.chain_all else None,
                                  stitch=a.stitch_max_link if a.stitch else None, net=(a.net_space, a.net_fill, a.net_subset, a.net_class, class_filter, a.lift) if a.net else None,
-                                 chain_costs=a.chain_costs or None)), flush=True)
+                                 chain_costs=a.chain_costs or None, chain_overlap=a.chain_overlap)), flush=True)
             continue
         for b in a.batches.split(","):
             E.set_option("gapped_greedy_batch", int(b))
