@@ -1030,6 +1030,128 @@ size_t sa_trim_chains(const sa_segment_pair* hsps, size_t n_hsps, const uint32_t
                       sa_trim_chain** chains, sa_trim_link** links, size_t* n_links, sa_trim_stats* stats);
 void sa_free_trim(sa_segment_pair* out_hsps, sa_trim_chain* chains, sa_trim_link* links);
 
+/* ---- filling the links of chains with HSPs from an exhaustive diagonal sweep (additive; restated by
+ *      tests/cpp/fill_check.c and tests/chain_fill_model.py) ---------------------------------------------------------------
+ *
+ * sa_fill_chains looks into the space between consecutive members of a chain, where the seeded path found nothing, scans every
+ * diagonal of it from end to end without a seed, and splices the best collinear chain of what it finds between the two members.  In
+ * the spirit of LASTZ's --inner; the semantics are this project's own and are NOT claimed to equal LASTZ's.  It needs a resident
+ * target block and query buffer, like sa_stitch_chains, whose errors it gives without one.
+ *   Link between consecutive members m, m' of a chain: sa_stitch_chains's rectangle, dt = rs_m' - re_m target bases from re_m by
+ *     dq = qs_m' - qe_m query bases from qe_m.
+ *   Scan: the rectangle's diagonals are d = i - j for d = -(dq - 1) .. dt - 1, 0 <= i < dt, 0 <= j < dq.  The cells of a diagonal are
+ *     k = 0 .. n - 1 from its first cell (i0, j0) = (max(d, 0), max(-d, 0)) inside the rectangle; cell k has the weight
+ *     w_k = sub_mat[X * 8 + Y] over the resident plain codes X = T[re_m + i0 + k], Y = Q[qe_m + j0 + k], sub_mat being
+ *     sa_initialize_processor's.  State: int32 s = 0, b = 0, and start, bend.  For every k in order:
+ *       1. if X or Y is the separator (7): flush, reset (s = b = 0), next cell;
+ *       2. if s == 0 and b == 0: start = k;
+ *       3. s += w_k;
+ *       4. if s > b: b = s, bend = k;
+ *       5. if s <= 0 or b - s > xdrop: flush, reset (the next segment starts at k + 1 at the earliest);
+ *       6. after the diagonal's last cell: flush.
+ *     Flush: if b >= thresh, the HSP {ref_start = re_m + i0 + start, query_start = qe_m + j0 + start, len = bend - start, score = b}
+ *     is found.
+ *     Consequences: the segments of a diagonal are disjoint and ascending; every proper prefix and every suffix of a segment scores
+ *     > 0; no prefix of a segment lies more than xdrop below an earlier one; score is the exact matrix sum of the segment's columns;
+ *     nothing leaves the rectangle, so a found HSP never overlaps m or m'.  There is no entropy adjustment.
+ *     Order of the found HSPs: by link in entry order, then d ascending, then i ascending.
+ *   Per link: it is swept only when neither side is 0, neither side is above max_side (otherwise SA_FILL_LONG) and
+ *     dt * dq <= max_cells (otherwise SA_FILL_LARGE).  A swept link that holds more than max_link_hsps HSPs is SA_FILL_CROWDED and
+ *     is treated as holding none (its record still says how many there were).
+ *   Choosing the fill: the found HSPs of all links are chained with sa_chain_hsps_costs's semantics exactly, the group being the link
+ *     index: p's diag_pen, anti_pen and max_gap and g apply, min_score = min_fill.  (The entry calls sa_chain_hsps_costs for that, in
+ *     batches of whole links of at most 1 << 22 HSPs, after it has given its slot back.)  A link's best chain, if it has one, is
+ *     spliced between m and m'.  The penalties pen(m, h_1) and pen(h_k, m') at the two ends are NOT part of the choice.
+ *   Validation (a message and exit code 1): the limits of sa_stitch_chains on chains, member entries, first[] and the members' place
+ *     inside the block; consecutive members satisfy re <= rs' and qe <= qs' (chains with overlaps go through sa_trim_chains first, and
+ *     the message says so); thresh >= 1, xdrop >= 0, max_side <= 1 << 20, max_cells <= 1 << 36, max_link_hsps <= 1 << 22;
+ *     max_side * A < 2^31 with A the largest |sub_mat entry| over the codes 0 .. 6, so that s stays inside int32; p and g as the
+ *     chaining entries check them; unknown flag bits.
+ *   Output, shaped as sa_trim_chains's so that every later stage takes it as it is (members = 0 .. E - 1, first = first_out):
+ *     one sa_segment_pair per entry of the filled chains, chain by chain: a member is its input HSP bit for bit, a fill is a found HSP;
+ *     first_out[n_chains + 1]; origin[E]: the input HSP index of a member, SA_FILL_NONE for a fill; per chain its score = the sum of
+ *     its entries' scores minus the sum over consecutive entries of pen' (the diagonal term, anti_pen and the table on the gaps, the
+ *     formula of sa_trim_chain.score), the fills spliced into it and their bases (len + 1).  With SA_FILL_LINKS one record per link
+ *     in entry order; with SA_FILL_HSPS every found HSP of the links that are not crowded, in the order above, with its link index.
+ *     After the call consecutive entries of a chain satisfy sa_chain_hsps's relation; a chain with nothing to fill is returned entry
+ *     for entry.
+ * Out of scope: equality with --inner, seeds inside the rectangle, the entropy filter, the end penalties in the choice of a fill,
+ * filling before the first or after the last member, re-chaining whole groups with the new HSPs. */
+#define SA_FILL_LINKS 1u   /* return the links */
+#define SA_FILL_HSPS 2u    /* return the found HSPs */
+#define SA_FILL_LONG 1u    /* dt or dq above max_side: not swept */
+#define SA_FILL_LARGE 2u   /* dt * dq above max_cells: not swept */
+#define SA_FILL_CROWDED 4u /* more than max_link_hsps HSPs: treated as holding none */
+#define SA_FILL_NONE 0xFFFFFFFFu
+
+typedef struct sa_fill_params {
+    int32_t thresh;         /* an HSP scores at least this; >= 1 (the defaults of a NULL: 3000) */
+    int32_t xdrop;          /* >= 0 (910) */
+    uint32_t max_side;      /* 0 = 32 768; at most 1 << 20 */
+    uint32_t max_link_hsps; /* 0 = 65 536; at most 1 << 22 */
+    uint64_t max_cells;     /* per link; 0 = 1 << 30; at most 1 << 36 */
+    int64_t min_fill;       /* a link's chain that scores less is not spliced (0) */
+} sa_fill_params;
+
+typedef struct sa_fill_chain {
+    int64_t score;       /* entry scores less the penalties between consecutive entries */
+    uint32_t fills;      /* found HSPs spliced into the chain */
+    uint32_t fill_bases; /* their bases */
+} sa_fill_chain;
+
+typedef struct sa_fill_link { /* 32 bytes */
+    uint32_t dt, dq;
+    uint32_t flags;  /* SA_FILL_LONG / _LARGE / _CROWDED or 0 */
+    uint32_t n_hsps; /* HSPs found (also for a crowded link) */
+    uint32_t n_fill; /* of them spliced */
+    uint32_t pad;
+    uint64_t cells;  /* dt * dq, 0 for a link that was not swept */
+} sa_fill_link;
+
+typedef struct sa_fill_hsp { /* 24 bytes */
+    uint32_t ref_start, query_start, len;
+    int32_t score;
+    uint32_t link; /* index of the link in entry order */
+    uint32_t pad;
+} sa_fill_hsp;
+
+typedef struct sa_fill_stats {
+    uint64_t links;
+    uint64_t swept;
+    uint64_t long_links, large_links, crowded_links;
+    uint64_t cells;        /* summed over the swept links */
+    uint64_t hsps;         /* found in the links that are not crowded */
+    uint64_t fills;        /* spliced */
+    uint64_t filled_links; /* links that got a fill */
+    double count_ms;       /* device time of the count passes with their prefix sums */
+    double emit_ms;        /* device time of the emit passes */
+    double chain_ms;       /* kernel_ms of the sa_chain_hsps_costs calls */
+} sa_fill_stats;
+#ifdef __cplusplus
+static_assert(sizeof(sa_fill_params) == 32, "sa_fill_params is 32 bytes");
+static_assert(sizeof(sa_fill_chain) == 16, "sa_fill_chain is 16 bytes");
+static_assert(sizeof(sa_fill_link) == 32, "sa_fill_link is 32 bytes");
+static_assert(sizeof(sa_fill_hsp) == 24, "sa_fill_hsp is 24 bytes");
+static_assert(sizeof(sa_fill_stats) == 96, "sa_fill_stats is 96 bytes");
+#else
+_Static_assert(sizeof(sa_fill_params) == 32, "sa_fill_params is 32 bytes");
+_Static_assert(sizeof(sa_fill_chain) == 16, "sa_fill_chain is 16 bytes");
+_Static_assert(sizeof(sa_fill_link) == 32, "sa_fill_link is 32 bytes");
+_Static_assert(sizeof(sa_fill_hsp) == 24, "sa_fill_hsp is 24 bytes");
+_Static_assert(sizeof(sa_fill_stats) == 96, "sa_fill_stats is 96 bytes");
+#endif
+
+/* Returns the number of entries E.  *out_hsps and *origin (E entries), *first_out (n_chains + 1 entries), *chains (n_chains entries),
+ * with SA_FILL_LINKS *links (*n_links entries) and with SA_FILL_HSPS *found (*n_found entries; each pair nullable without its flag)
+ * are malloc-ed and released with sa_free_fill; each is NULL when it would be empty.  p, fp: NULL takes the defaults; g: NULL for no
+ * table; stats: nullable.  Slots and thread safety are those of sa_stitch_chains; the slot is given back before the chaining calls. */
+size_t sa_fill_chains(const sa_segment_pair* hsps, size_t n_hsps, const uint32_t* members, const uint32_t* first, size_t n_chains, int rev,
+                      uint32_t buffer, const sa_chain_params* p, const sa_chain_gap_costs* g, const sa_fill_params* fp, uint32_t flags,
+                      sa_segment_pair** out_hsps, uint32_t** first_out, uint32_t** origin, sa_fill_chain** chains, sa_fill_link** links,
+                      size_t* n_links, sa_fill_hsp** found, size_t* n_found, sa_fill_stats* stats);
+void sa_free_fill(sa_segment_pair* out_hsps, uint32_t* first_out, uint32_t* origin, sa_fill_chain* chains, sa_fill_link* links,
+                  sa_fill_hsp* found);
+
 /* ---- stitching the members of a chain into one gapped alignment (additive; restated by tests/cpp/stitch_check.c and
  *      tests/stitch_model.py) ----------------------------------------------------------------------------------------------
  *

@@ -18,6 +18,7 @@
 //   api_netsubset.hip  sa_net_subset: the fills of a net cut into clipped, rescored sub-chains (netsubset.hip)
 //   api_netclass.hip   sa_net_classify: the fills of a net classed against their parents on the other axis, with duplication and the filter (netclass.hip)
 //   api_lift.hip       sa_lift_intervals: intervals of one axis carried through chains to the other axis (lift.hip)
+//   api_fill.hip       sa_fill_chains: the links of chains filled with HSPs from a sweep of every diagonal (fill.hip)
 //   post_host.h        what those seven share on the host: event timing, checked launches, buffer carving, caller-owned arrays, trace batches
 //   gapped.hip         kernels of the gapped entries: y-drop extension of a side, trace sweep, path walk (gapped.h)
 //   cover.hip          kernels and rocPRIM steps of the greedy cover index; its sort and scan wrappers also serve api_hspchain.hip (gapped.h)
@@ -366,6 +367,7 @@ struct Slot {
     DevBuf<uint8_t> netclass;         // sa_net_classify (api_netclass.hip, netclass.hip): the fills, the blocks of both axes, the events and everything made of them
     // sa_lift_intervals (api_lift.hip, lift.hip): the chains, the intervals and what is made per interval; the hits; the output blocks
     DevBuf<uint8_t> lift, lift_hits, lift_out;
+    DevBuf<uint8_t> fill;             // sa_fill_chains (api_fill.hip, fill.hip): a batch's tasks, counts and offsets, and an emit group's HSPs
     bool early = false;               // taken from the pool that serves sa_chain_hsps before InitializeProcessor (pool.hip)
 };
 

@@ -141,6 +141,7 @@ void slot_destroy(Slot& s) {
     s.lift.release("lift");
     s.lift_hits.release("lift hits");
     s.lift_out.release("lift blocks");
+    s.fill.release("fill");
     s.cand_list.release("candidate list");
     s.l2_list.release("second-level list");
     s.audit.release("audit list");

@@ -1,5 +1,5 @@
 // post_host.h -- the host helpers that the post-processing entries share (api_gapped.hip, api_hspchain.hip, api_stitch.hip, api_net.hip,
-// api_netsubset.hip, api_netclass.hip, api_lift.hip): device time between events, profiled and checked launches, carving a slot buffer, malloc-ed arrays for
+// api_netsubset.hip, api_netclass.hip, api_lift.hip, api_fill.hip): device time between events, profiled and checked launches, carving a slot buffer, malloc-ed arrays for
 // the caller, the resident block as kernel arguments, the checked gap-cost table as its device image, and the trace batches' packing and
 // runs.  Host code only, everything inline or a template.
 #pragma once

@@ -46,6 +46,7 @@ C_ABI_SYMBOLS = [
     "sa_chain_hsps", "sa_free_chain", "sa_chain_hsps_all", "sa_free_chain_all",
     "sa_chain_hsps_costs", "sa_chain_hsps_all_costs", "sa_chain_gap_preset",
     "sa_chain_hsps_ovl", "sa_chain_hsps_all_ovl", "sa_trim_chains", "sa_free_trim",
+    "sa_fill_chains", "sa_free_fill",
     "sa_stitch_chains", "sa_free_stitch",
     "sa_net_chains", "sa_free_net",
     "sa_net_subset", "sa_free_net_subset",
@@ -122,6 +123,27 @@ TRIM_LINKS = 1
 class TrimStats(C.Structure):  # sa_trim_stats
     _fields_ = [("chains", C.c_uint64), ("members", C.c_uint64), ("links", C.c_uint64), ("trimmed_links", C.c_uint64),
                 ("cut_members", C.c_uint64), ("bases_cut", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
+FILL_CHAIN_DTYPE = np.dtype([("score", "<i8"), ("fills", "<u4"), ("fill_bases", "<u4")])  # sa_fill_chain
+FILL_LINK_DTYPE = np.dtype([("dt", "<u4"), ("dq", "<u4"), ("flags", "<u4"), ("n_hsps", "<u4"), ("n_fill", "<u4"), ("pad", "<u4"),
+                            ("cells", "<u8")])  # sa_fill_link
+FILL_HSP_DTYPE = np.dtype([("ref_start", "<u4"), ("query_start", "<u4"), ("len", "<u4"), ("score", "<i4"), ("link", "<u4"),
+                           ("pad", "<u4")])  # sa_fill_hsp
+FILL_LINKS, FILL_HSPS = 1, 2
+FILL_LONG, FILL_LARGE, FILL_CROWDED = 1, 2, 4
+FILL_NONE = 0xFFFFFFFF  # origin of an entry that is a fill
+
+
+class FillParams(C.Structure):  # sa_fill_params
+    _fields_ = [("thresh", C.c_int32), ("xdrop", C.c_int32), ("max_side", C.c_uint32), ("max_link_hsps", C.c_uint32),
+                ("max_cells", C.c_uint64), ("min_fill", C.c_int64)]
+
+
+class FillStats(C.Structure):  # sa_fill_stats
+    _fields_ = [("links", C.c_uint64), ("swept", C.c_uint64), ("long_links", C.c_uint64), ("large_links", C.c_uint64),
+                ("crowded_links", C.c_uint64), ("cells", C.c_uint64), ("hsps", C.c_uint64), ("fills", C.c_uint64),
+                ("filled_links", C.c_uint64), ("count_ms", C.c_double), ("emit_ms", C.c_double), ("chain_ms", C.c_double)]
 
 
 class ChainStats(C.Structure):
@@ -410,6 +432,12 @@ def lib():
                                  C.POINTER(ChainGapCosts), C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                  C.POINTER(C.c_size_t), C.POINTER(TrimStats)]
     L.sa_free_trim.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sa_fill_chains.restype = C.c_size_t
+    L.sa_fill_chains.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(ChainParams),
+                                 C.POINTER(ChainGapCosts), C.POINTER(FillParams), C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                 C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                 C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(FillStats)]
+    L.sa_free_fill.argtypes = [C.c_void_p] * 6
     L.sa_chain_gap_preset.restype = C.c_int
     L.sa_chain_gap_preset.argtypes = [C.c_char_p, C.POINTER(ChainGapCosts)]
     L.sa_stitch_chains.restype = C.c_size_t
@@ -840,6 +868,38 @@ def TrimChains(hsps, members, first, rev, buffer=0, diag_pen=0, anti_pen=0, gap_
     res_l = _chain_take(lk, nl.value, TRIM_LINK_DTYPE)
     lib().sa_free_trim(out, ch, lk)
     return (res_h, res_c, res_l, _flat(st)) if links else (res_h, res_c, _flat(st))
+
+
+def FillChains(hsps, members, first, rev, buffer=0, thresh=3000, xdrop=910, diag_pen=0, anti_pen=0, max_gap=0, gap_costs=None, min_fill=0,
+               max_side=0, max_cells=0, max_link_hsps=0, links=False, found=False):
+    """Fills the links of chains with HSPs from a sweep of every diagonal of the space between consecutive members (sa_fill_chains;
+    contract in include/segalign_amd.h, DESIGN.md 25).  hsps, members, first, rev, buffer as for TrimChains; thresh, xdrop: the scan;
+    the penalties, max_gap and gap_costs choose a link's fill as ChainHsps would, min_fill is its least score; max_side, max_cells,
+    max_link_hsps: 0 takes the default.  -> (SEG_DTYPE entries of the filled chains: go on with members = arange(E) and first_out;
+    uint32 first_out; uint32 origin (FILL_NONE for a fill); FILL_CHAIN_DTYPE chains; with links=True the FILL_LINK_DTYPE links; with
+    found=True the FILL_HSP_DTYPE found HSPs; stats dict)."""
+    h = np.ascontiguousarray(hsps, dtype=SEG_DTYPE)
+    mem, fst = np.ascontiguousarray(members, dtype=np.uint32), np.ascontiguousarray(first, dtype=np.uint32)
+    if fst.size == 0 or (fst.size and int(fst[-1]) != mem.size):
+        raise ValueError("first: one more entry than chains, the last one the number of members")
+    p = ChainParams(int(diag_pen), int(anti_pen), int(max_gap), 0, 0)
+    fp = FillParams(int(thresh), int(xdrop), int(max_side), int(max_link_hsps), int(max_cells), int(min_fill))
+    out, fo, org, ch, lk, fd = (C.c_void_p() for _ in range(6))
+    nl, nf, st = C.c_size_t(0), C.c_size_t(0), FillStats()
+    e = lib().sa_fill_chains(h.ctypes.data if h.size else None, h.size, mem.ctypes.data if mem.size else None, fst.ctypes.data, fst.size - 1,
+                             int(bool(rev)), int(buffer), C.byref(p), C.byref(chain_gap_costs(gap_costs)) if gap_costs is not None else None,
+                             C.byref(fp), (FILL_LINKS if links else 0) | (FILL_HSPS if found else 0), C.byref(out), C.byref(fo), C.byref(org),
+                             C.byref(ch), C.byref(lk), C.byref(nl), C.byref(fd), C.byref(nf), C.byref(st))
+    res = [_chain_take(out, e, SEG_DTYPE), _chain_take(fo, fst.size if fo.value else 0, np.uint32), _chain_take(org, e, np.uint32),
+           _chain_take(ch, fst.size - 1, FILL_CHAIN_DTYPE)]
+    if links:
+        res.append(_chain_take(lk, nl.value, FILL_LINK_DTYPE))
+    if found:
+        res.append(_chain_take(fd, nf.value, FILL_HSP_DTYPE))
+    lib().sa_free_fill(out, fo, org, ch, lk, fd)
+    if res[1].size == 0:
+        res[1] = np.zeros(1, dtype=np.uint32)
+    return tuple(res) + (_flat(st),)
 
 
 def chain_csr(members):

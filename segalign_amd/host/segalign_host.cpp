@@ -53,6 +53,12 @@ struct Config {  // src/graph.h:32-76 with the defaults of src/main.cpp:61-124
     sa_chain_gap_costs chain_costs;  // (sa_chain_hsps_costs / sa_chain_hsps_all_costs)
     uint32_t chain_overlap = 0;  // --gpu_chain_overlap[=N] (with --gpu_chain or --gpu_chain_all): chain members may share up to N bases
                                  // (sa_chain_hsps_ovl / sa_chain_hsps_all_ovl) and the chains are trimmed (sa_trim_chains); 0: off
+    bool chain_fill = false;  // --gpu_chain_fill[=thresh[,xdrop]] (with --gpu_chain or --gpu_chain_all): the links of the chains, trimmed ones with
+                              // --gpu_chain_overlap, are swept for HSPs the seeds missed and filled (sa_fill_chains); a
+                              // .filled.chain / .filled.chains file next to every .chain / .chains file, and every later stage takes the filled chains
+    int fill_thresh = 3000, fill_xdrop = 910;
+    uint32_t fill_side = 0;   // --gpu_chain_fill_side=N: sa_fill_params.max_side
+    bool fill_side_set = false;
     bool gpu_stitch = false;  // --gpu_stitch[=max_link] (with --gpu_chain or --gpu_chain_all): a .stitched.maf file next to every .chain / .chains file (sa_stitch_chains)
     uint32_t stitch_max_link = 0;  // sa_stitch_params.max_link; 0: the engine's default
     bool stitch_min_set = false;
@@ -380,22 +386,57 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
                 untrimmed_idx = idx;
                 for (size_t k = 0; k < idx.size(); k++) idx[k] = (uint32_t)k;
             }
-            const std::vector<sa_segment_pair>& cv = cfg.chain_overlap ? trimmed : v;  // what idx indexes
-            if (cfg.gpu_chain) {
-                for (size_t k = 0; k < idx.size(); k++) emit(cv[idx[k]]);
-            } else {
-                for (size_t c = 0; c < crec.size(); c++) {  // the order sa_chain_hsps_all returns, on both strands
-                    fprintf(f, "#chain %zu group=%u score=%lld members=%u joined=%d\n", c, crec[c].group, (long long)crec[c].score, crec[c].n_members,
-                            crec[c].joined >= 0 ? 1 : 0);
-                    for (size_t k = crec[c].first_member; k < (size_t)crec[c].first_member + crec[c].n_members; k++) emit(cv[idx[k]]);
-                    if (cfg.gpu_net) {
-                        cscore.push_back(crec[c].score);
-                        ctarget.push_back((uint32_t)(pairs[crec[c].group] >> 32));
-                        cquery.push_back((uint32_t)pairs[crec[c].group]);
+            auto write_chains = [&](const std::vector<sa_segment_pair>& hv) {  // the chains of idx, cfirst and crec over hv, into f
+                if (cfg.gpu_chain) {
+                    for (size_t k = 0; k < idx.size(); k++) emit(hv[idx[k]]);
+                } else {
+                    for (size_t c = 0; c < crec.size(); c++) {  // the order sa_chain_hsps_all returns, on both strands
+                        fprintf(f, "#chain %zu group=%u score=%lld members=%u joined=%d\n", c, crec[c].group, (long long)crec[c].score, crec[c].n_members,
+                                crec[c].joined >= 0 ? 1 : 0);
+                        for (size_t k = crec[c].first_member; k < (size_t)crec[c].first_member + crec[c].n_members; k++) emit(hv[idx[k]]);
                     }
                 }
-            }
+            };
+            write_chains(cfg.chain_overlap ? trimmed : v);
             fclose(f);
+            // with --gpu_chain_fill the space between consecutive members is swept for what the seeds missed.  From here on
+            // the chains' HSP vector is the filled one, one entry per member or fill, and the chains' scores are the filled chains'
+            std::vector<sa_segment_pair> filled;
+            std::vector<uint32_t> fill_vkey;  // per entry: the index in v of the member it is, or of the member its fill follows
+            if (cfg.chain_fill) {
+                const std::vector<sa_segment_pair>& hv = cfg.chain_overlap ? trimmed : v;
+                const sa_fill_params fp = {cfg.fill_thresh, cfg.fill_xdrop, cfg.fill_side, 0, 0, 0};
+                sa_segment_pair* fh = nullptr;
+                uint32_t *ffirst = nullptr, *forigin = nullptr;
+                sa_fill_chain* fc = nullptr;
+                const size_t fe = sa_fill_chains(hv.data(), hv.size(), idx.data(), cfirst.data(), cfirst.size() - 1, rev, buffer, &cp, costs, &fp, 0, &fh,
+                                                 &ffirst, &forigin, &fc, nullptr, nullptr, nullptr, nullptr, nullptr);
+                filled.assign(fh, fh + fe);
+                fill_vkey.resize(fe);
+                for (size_t k = 0; k < fe; k++)
+                    fill_vkey[k] = forigin[k] == SA_FILL_NONE ? fill_vkey[k - 1] : cfg.chain_overlap ? untrimmed_idx[forigin[k]] : forigin[k];
+                for (size_t c = 0; c + 1 < cfirst.size(); c++) cfirst[c + 1] = ffirst[c + 1];
+                for (size_t c = 0; c < crec.size(); c++) {
+                    crec[c].score = fc[c].score;
+                    crec[c].first_member = cfirst[c];
+                    crec[c].n_members = cfirst[c + 1] - cfirst[c];
+                }
+                sa_free_fill(fh, ffirst, forigin, fc, nullptr, nullptr);
+                idx.resize(fe);
+                for (size_t k = 0; k < fe; k++) idx[k] = (uint32_t)k;
+                std::string fname = base + (cfg.gpu_chain ? ".filled.chain" : ".filled.chains");
+                f = fopen((cfg.outdir + "/" + fname).c_str(), "w");
+                if (!f) die(7, "cant open file: %s", fname.c_str());
+                write_chains(filled);
+                fclose(f);
+            }
+            const std::vector<sa_segment_pair>& cv = cfg.chain_fill ? filled : cfg.chain_overlap ? trimmed : v;  // what idx indexes
+            if (cfg.gpu_net)
+                for (size_t c = 0; c < crec.size(); c++) {
+                    cscore.push_back(crec[c].score);
+                    ctarget.push_back((uint32_t)(pairs[crec[c].group] >> 32));
+                    cquery.push_back((uint32_t)pairs[crec[c].group]);
+                }
             // every chain of a CSR as one alignment through its members, in --gpu_maf's block layout, into the file sname
             auto write_stitched = [&](const std::string& sname, const sa_segment_pair* sh, size_t n_sh, const uint32_t* smem, const uint32_t* sfirst,
                                       size_t n_sc) {
@@ -579,7 +620,11 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
                 sa_free_net(nf);
             }
             kept.reserve(idx.size());
-            if (cfg.chain_overlap) {  // the trimmed members in the order of their HSPs within v
+            if (cfg.chain_fill) {  // the members in the order of their HSPs within v, every fill behind the member it follows
+                std::vector<uint32_t> ord(idx);
+                std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return fill_vkey[x] < fill_vkey[y]; });
+                for (uint32_t k : ord) kept.push_back(filled[k]);
+            } else if (cfg.chain_overlap) {  // the trimmed members in the order of their HSPs within v
                 std::vector<uint32_t> ord(idx);
                 std::sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return untrimmed_idx[x] < untrimmed_idx[y]; });
                 for (uint32_t k : ord) kept.push_back(trimmed[k]);
@@ -699,6 +744,10 @@ static void usage() {
             "      less than half of the shorter, on either sequence, as HSPs on the two sides of an indel do; every overlap is then cut where the\n"
             "      two together score best, so the .chain / .chains files hold the trimmed members with their exact scores and the exact chain\n"
             "      scores, and every later stage of the run gets those)\n"
+            "  --gpu_chain_fill[=thresh[,xdrop]] (with --gpu_chain or --gpu_chain_all: every diagonal of the space between consecutive members of a\n"
+            "      chain is scanned for ungapped HSPs the seeds missed, default 3000,910, and the best collinear chain of them is spliced in; a\n"
+            "      .filled.chain / .filled.chains file next to each .chain / .chains file, and every later stage works on the filled chains)\n"
+            "  --gpu_chain_fill_side=N (with --gpu_chain_fill: a space with a side above N is not scanned; default 32768, at most 1048576)\n"
             "  --gpu_stitch[=max_link] (with --gpu_chain or --gpu_chain_all: a .stitched.maf file next to each .chain / .chains file with every\n"
             "      chain as one alignment through all its members, the stretch between two members aligned globally with --gap=O,E; a chain\n"
             "      is cut where a side of that stretch exceeds max_link (default and at most 2048) or holds a record boundary)\n"
@@ -841,6 +890,29 @@ int main(int argc, char** argv) {
             if (endp == v.c_str() || *endp || n < 1 || n > SA_CHAIN_MAX_OVERLAP) { fprintf(stderr, "bad --gpu_chain_overlap=%s (1 .. %d)\n", v.c_str(), SA_CHAIN_MAX_OVERLAP); return 1; }
             cfg.chain_overlap = (uint32_t)n;
         }
+        else if (!strcmp(a, "--gpu_chain_fill")) cfg.chain_fill = true;
+        else if (opt(a, "--gpu_chain_fill", v)) {
+            char* endp = nullptr;
+            const long long th = strtoll(v.c_str(), &endp, 10);
+            long long xd = cfg.fill_xdrop;
+            bool ok = endp != v.c_str() && (*endp == 0 || *endp == ',') && th >= 1 && th <= INT32_MAX;
+            if (ok && *endp == ',') {
+                const char* x = endp + 1;
+                xd = strtoll(x, &endp, 10);
+                ok = endp != x && *endp == 0 && xd >= 0 && xd <= INT32_MAX;
+            }
+            if (!ok) { fprintf(stderr, "bad --gpu_chain_fill=%s (thresh[,xdrop]; thresh at least 1, xdrop at least 0)\n", v.c_str()); return 1; }
+            cfg.chain_fill = true;
+            cfg.fill_thresh = (int)th;
+            cfg.fill_xdrop = (int)xd;
+        }
+        else if (opt(a, "--gpu_chain_fill_side", v)) {
+            char* endp = nullptr;
+            const long long n = strtoll(v.c_str(), &endp, 10);
+            if (endp == v.c_str() || *endp || n < 1 || n > (1 << 20)) { fprintf(stderr, "bad --gpu_chain_fill_side=%s (1 .. %d)\n", v.c_str(), 1 << 20); return 1; }
+            cfg.fill_side = (uint32_t)n;
+            cfg.fill_side_set = true;
+        }
         else if (opt(a, "--gpu_chain_costs", v)) {
             std::string err;
             if (sa_chain_gap_preset(v.c_str(), &cfg.chain_costs) != 0 && !read_linear_gap(v, cfg.chain_costs, err)) {
@@ -922,6 +994,8 @@ int main(int argc, char** argv) {
     if (cfg.chain_min_set && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_chain_min needs --gpu_chain_all\n"); return 1; }
     if (cfg.chain_costs_set && !cfg.gpu_chain && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_chain_costs needs --gpu_chain or --gpu_chain_all\n"); return 1; }
     if (cfg.chain_overlap && !cfg.gpu_chain && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_chain_overlap needs --gpu_chain or --gpu_chain_all\n"); return 1; }
+    if (cfg.chain_fill && !cfg.gpu_chain && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_chain_fill needs --gpu_chain or --gpu_chain_all\n"); return 1; }
+    if (cfg.fill_side_set && !cfg.chain_fill) { fprintf(stderr, "--gpu_chain_fill_side needs --gpu_chain_fill\n"); return 1; }
     if (cfg.gpu_stitch && !cfg.gpu_chain && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_stitch needs --gpu_chain or --gpu_chain_all\n"); return 1; }
     if (cfg.stitch_min_set && !cfg.gpu_stitch) { fprintf(stderr, "--gpu_stitch_min needs --gpu_stitch\n"); return 1; }
     if (cfg.gpu_net && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_net needs --gpu_chain_all\n"); return 1; }

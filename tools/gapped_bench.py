@@ -31,6 +31,12 @@ the chains before min_score, the chains, joined chains and members kept, the dou
 the gapped times on the kept chains' members beside those on the best chain and on all HSPs.  The chains, members and chain_of are
 checked against the numpy model (tests/hsp_chain_all_model.py) once per run, on the f and pred the --chain check computed.
 
+With --fill [--fill-thresh N] (which implies --chain-all) the links of the kept chains go through sa_fill_chains under
+--chain-pen: the line then adds the links by flag, the cells, count / emit / chain ms (the run with the least sweep time) and G cells/s
+over both passes, the HSPs found, the fills and the links filled, and sa_stitch_chains's long links and records on the chains before
+and after filling.  A prefix of the chains, links of at most 2^28 cells together, is checked against tests/chain_fill_model.py once
+per run.
+
 With --stitch [--stitch-max-link N] (which implies --chain-all) the kept chains go through sa_stitch_chains: the line then
 adds the links by sweep instance, the broken links by reason, the cells, member / sweep / walk ms, giga-cells per second of the sweep, the
 trace bytes and batches, and the target bases the stitched records span beside those the gapped alignments of the same members span.
@@ -58,7 +64,7 @@ launches (the sort's and the running maximum's come on top).  The records, hits 
 sub-chains, under both flags, are checked against the model (tests/lift_model.py) once per run.
 
   python tools/gapped_bench.py [--workloads standin,lumpy] [--repeat 3] [--align] [--greedy] [--batches 1024,2048,...]
-                               [--pieces N] [--max-extent M] [--chain] [--chain-pen D,A] [--chain-costs T] [--chain-overlap N] [--chain-all] [--chain-min N] [--stitch] [--stitch-max-link N]
+                               [--pieces N] [--max-extent M] [--chain] [--chain-pen D,A] [--chain-costs T] [--chain-overlap N] [--fill] [--fill-thresh N] [--chain-all] [--chain-min N] [--stitch] [--stitch-max-link N]
                                [--net] [--net-space N] [--net-fill N] [--net-subset] [--net-class] [--net-class-filter S,T,Z,A,F] [--lift[=N]]
 """
 import argparse
@@ -229,6 +235,45 @@ def stitch_fields(hsps, members, repeat, max_link):
             "kept_gapped_alignments": int(grecs.size), "stitch_model_checked": True, "stitch_model_s": round(model_s, 1)}
 
 
+def fill_fields(hsps, members, repeat, pen, thresh):
+    """sa_fill_chains on the kept chains, the run with the least count and emit time; sa_stitch_chains's long links and
+    records on the chains before and after; a prefix of the chains (links of at most 2^28 cells together) checked against the model."""
+    import chain_fill_model as F
+    mem, first = E.chain_csr(members)
+    kw = dict(thresh=thresh, diag_pen=pen[0], anti_pen=pen[1])
+    best = None
+    for _ in range(repeat):
+        t0 = time.perf_counter()
+        r = E.FillChains(hsps, mem, first, False, 0, links=True, **kw)
+        wall = (time.perf_counter() - t0) * 1e3
+        if best is None or r[5]["count_ms"] + r[5]["emit_ms"] < best[0][5]["count_ms"] + best[0][5]["emit_ms"]:
+            best = (r, wall)
+    (out, first_out, origin, ch, links, st), wall = best
+    before = E.StitchChains(hsps, mem, first, False, 0)[2]
+    after = E.StitchChains(out, np.arange(out.size, dtype=np.uint32), first_out, False, 0)[2]
+    # the model on the first chains: as many as keep the scalar checker below 2^28 cells
+    nl = np.maximum(np.diff(first.astype(np.int64)) - 1, 0)
+    cells = np.concatenate([[0], np.cumsum(links["cells"].astype(np.int64))])[np.cumsum(nl)]  # the cells up to and including chain c
+    k = min(max(1, int(np.searchsorted(cells, 1 << 28, side="right"))), first.size - 1)
+    t0 = time.perf_counter()
+    got = E.FillChains(hsps, mem[:first[k]], first[:k + 1], False, 0, links=True, found=True, **kw)
+    want = F.fill(E.copy_ref_codes(), E.copy_query_codes(0, False), SUB, hsps, mem[:first[k]], first[:k + 1], **kw)
+    model_s = time.perf_counter() - t0
+    for g, w in zip(got[:6], want):
+        if g.size != w.size or not all(np.array_equal(g[f], w[f]) for f in (w.dtype.names or ())) or (not w.dtype.names and not np.array_equal(g, w)):
+            raise SystemExit("sa_fill_chains differs from the model")
+    sweep_ms = st["count_ms"] + st["emit_ms"]
+    return {"fill_thresh": int(thresh), "fill_links": int(st["links"]), "fill_swept": int(st["swept"]), "fill_long": int(st["long_links"]),
+            "fill_large": int(st["large_links"]), "fill_crowded": int(st["crowded_links"]), "fill_cells": int(st["cells"]),
+            "fill_hsps_found": int(st["hsps"]), "fill_fills": int(st["fills"]), "fill_links_filled": int(st["filled_links"]),
+            "fill_bases": int(ch["fill_bases"].astype(np.int64).sum()), "fill_count_ms": round(st["count_ms"], 3), "fill_emit_ms": round(st["emit_ms"], 3),
+            "fill_chain_ms": round(st["chain_ms"], 3), "fill_call_ms": round(wall, 3),
+            "fill_gcells_per_s": round(2 * st["cells"] / (sweep_ms * 1e-3) / 1e9, 3) if sweep_ms > 0 else None,  # both passes sweep every cell
+            "fill_stitch_long_before": int(before["long_links"]), "fill_stitch_records_before": int(before["records"]),
+            "fill_stitch_long_after": int(after["long_links"]), "fill_stitch_records_after": int(after["records"]),
+            "fill_model_checked": True, "fill_model_chains": int(k), "fill_model_links": int(want[4].size), "fill_model_s": round(model_s, 1)}
+
+
 def subset_fields(hsps, mem, first, fills, repeat, pen, net_ms, peel_ms):
     """sa_net_subset on the fills of the net, the run with the least subset time, checked against the model."""
     import net_subset_model as NS
@@ -363,7 +408,7 @@ def net_fields(hsps, chains, members, repeat, net, peel_ms, dp_ms, pen=(0, 0)):
             "net_over_dp": round(st["net_ms"] / dp_ms, 4) if dp_ms > 0 else None, "net_model_checked": True, "net_model_s": round(model_s, 1)}
 
 
-def chain_all_fields(hsps, repeat, pen, min_score, dp, align, greedy, stitch=None, net=None):
+def chain_all_fields(hsps, repeat, pen, min_score, dp, align, greedy, stitch=None, net=None, fill=None):
     """sa_chain_hsps_all on the HSPs as one group, checked against the numpy model on the DP values `dp` that chain_fields checked, and
     the gapped entries on the kept chains' members."""
     import hsp_chain_all_model as A
@@ -389,6 +434,8 @@ def chain_all_fields(hsps, repeat, pen, min_score, dp, align, greedy, stitch=Non
         out.update(stitch_fields(hsps, members, repeat, stitch))
     if net is not None:
         out.update(net_fields(hsps, chains, members, repeat, net, st["peel_ms"], st["kernel_ms"], pen))
+    if fill is not None:
+        out.update(fill_fields(hsps, members, repeat, pen, fill))
     return out
 
 
@@ -458,7 +505,7 @@ def chain_overlap_fields(hsps, pen, costs, overlap, runs, plain_runs):
             "chain_overlap_model_checked": True, "chain_overlap_model_s": round(model_s, 1)}
 
 
-def chain_fields(hsps, repeat, pen, align, greedy, all_min=None, stitch=None, net=None, costs=None, overlap=0):
+def chain_fields(hsps, repeat, pen, align, greedy, all_min=None, stitch=None, net=None, costs=None, overlap=0, fill=None):
     """sa_chain_hsps on the HSPs as one group, checked against the numpy model, and the gapped entries on the chain's members; with
     all_min also chain_all_fields, with costs also chain_costs_fields (its runs alternate with the linear ones), with overlap also
     chain_overlap_fields (its runs alternate with the plain ones)."""
@@ -496,12 +543,12 @@ def chain_fields(hsps, repeat, pen, align, greedy, all_min=None, stitch=None, ne
         out.update(chain_overlap_fields(hsps, pen, costs, overlap, overlap_runs, cost_runs if costs else linear_runs))
     out.update(kept_fields(kept, repeat, align, greedy, "kept_"))
     if all_min is not None:
-        out.update(chain_all_fields(hsps, repeat, pen, all_min, (f, pred), align, greedy, stitch, net))
+        out.update(chain_all_fields(hsps, repeat, pen, all_min, (f, pred), align, greedy, stitch, net, fill))
     return out
 
 
 def run(name, repeat, align=False, greedy=False, with_sel=True, pieces=0, chain=None, chain_all_min=None, stitch=None, net=None, chain_costs=None,
-        chain_overlap=0):
+        chain_overlap=0, fill=None):
     t, q = workload(name)
     if greedy or pieces:
         E.set_option("debug", 1)  # sa_gapped_align_greedy then prints its edge count, the continuation its pieces
@@ -549,7 +596,7 @@ def run(name, repeat, align=False, greedy=False, with_sel=True, pieces=0, chain=
     if greedy:
         extra.update(greedy_fields(hsps, repeat, with_sel))
     if chain is not None:
-        extra.update(chain_fields(hsps, repeat, chain, align, greedy, chain_all_min, stitch, net, chain_costs, chain_overlap))
+        extra.update(chain_fields(hsps, repeat, chain, align, greedy, chain_all_min, stitch, net, chain_costs, chain_overlap, fill))
     E.ShutdownProcessor()
     if greedy or pieces:
         E.reset_option("debug")
@@ -588,6 +635,8 @@ def main():
                     help="with --net-class: min_score,min_top_score,min_size,min_ali,max_far of the filtered call")
     ap.add_argument("--lift", type=int, nargs="?", const=1 << 20, default=0, metavar="N",
                     help="also lift N intervals of the target through the sub-chains and through all chains (sa_lift_intervals); implies --net-subset")
+    ap.add_argument("--fill", action="store_true", help="also fill the links of the kept chains (sa_fill_chains); implies --chain-all")
+    ap.add_argument("--fill-thresh", type=int, default=3000, help="with --fill: thresh")
     a = ap.parse_args()
     if a.lift < 0 or a.lift > 1 << 26:
         ap.error("--lift takes 1 .. 1 << 26 intervals")
@@ -596,7 +645,7 @@ def main():
     class_filter = tuple(int(x) for x in a.net_class_filter.split(","))
     if len(class_filter) != 5:
         ap.error("--net-class-filter takes five values")
-    a.chain_all = a.chain_all or a.stitch or a.net
+    a.chain_all = a.chain_all or a.stitch or a.net or a.fill
     chain = tuple(int(x) for x in a.chain_pen.split(",")) if a.chain or a.chain_all else None
     if a.chain_costs and chain is None:
         ap.error("--chain-costs needs --chain")
@@ -610,7 +659,8 @@ def main():
         if not a.batches:
             print(json.dumps(run(name, a.repeat, a.align, a.greedy, pieces=a.pieces, chain=chain, chain_all_min=a.chain_min if a.chain_all else None,
                                  stitch=a.stitch_max_link if a.stitch else None, net=(a.net_space, a.net_fill, a.net_subset, a.net_class, class_filter, a.lift) if a.net else None,
-                                 chain_costs=a.chain_costs or None, chain_overlap=a.chain_overlap)), flush=True)
+                                 chain_costs=a.chain_costs or None, chain_overlap=a.chain_overlap, fill=a.fill_thresh if a.fill else None)),
+                  flush=True)
             continue
         for b in a.batches.split(","):
             E.set_option("gapped_greedy_batch", int(b))
