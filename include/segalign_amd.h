@@ -253,6 +253,7 @@ int sa_max_hits_for_mem(uint64_t total_global_mem);
  *   LDS-staged partition build is the default), work_gb (GiB of work arena per slot), arena_vmm, call_hits, call_hits_max
  * Test-only options (small capacities that force the overflow / fallback branches of the orchestration)
  *   l2_cap, spec_dedup, spec_recs, dedup_seg_max, no_small_dedup, chain_cap, chain_no_link, q2_limit_mb, audit_cap
+ *   fwd_keep          1: a context-table call keeps the class filter's hand-over list for sa_get_forwards (default 0: nothing is read back)
  *   cand_cap          records the candidate list of a batch is first sized for, in place of max(2^16, hits of the batch / 16)
  *   ent_cap           the same for the list of hits that need the entropy factor, in place of max(2^16, hits of the batch / 32)
  *   out_cap           the same for the survivor list of the call, in place of max(2^20, min(hits of the call, 2^26)); the kernels are
@@ -277,6 +278,22 @@ const char* sa_option_name(int i, int* test_only /* nullable */);
  * upper bounds. */
 size_t sa_get_audit(uint32_t* dst_pairs, size_t cap_pairs);
 
+/* With option fwd_keep = 1: after the last attempt of a context-table call (lookup path 2) the hand-over list of the class filter
+ * (level 1) is read back: the 256 sub-list counters and the first min(count, capacity) records of every sub-list, concatenated in
+ * sub-list order -- what the second level (the packed filter) walked.  Returns how many records the calling thread's last such call
+ * kept and copies min(that, cap_recs) of them; sub_counts256 (nullable) receives the 256 raw counters.  A record is 20 bytes, five
+ * little-endian uint32:
+ *   ref_loc, query_loc   the anchor (seed start + seed_size on either sequence)
+ *   hidx                 index of the hit in the call's hit order (query position ascending, table-run order inside a position)
+ *   state                the packed register {T : D} of the walk level 2 resumes: T (int16, high half) the running class score at the end
+ *                        of level 1's context, D (low half) = best - T >= 0.  The LEFT walk's (seed window bound + 58 bases), or the
+ *                        RIGHT walk's (54 bases) when flags == 1 under option l2_right_state
+ *   meta                 known | flags << 16.  flags bit 0: right side still alive at the end of its context, bit 1: left side; both
+ *                        settled but bestR + bestL >= hspthresh is sent as 3.  known = bestL when the right side is alive, else bestR
+ * The order inside a sub-list is the order of the appends; tests sort by hidx.  A call that never starts the filters (no hits) keeps
+ * an empty list.  With the option at 0 the list is empty. */
+size_t sa_get_forwards(void* dst_l2recs, size_t cap_recs, uint32_t* sub_counts256 /* nullable */);
+
 typedef struct sa_call_stats {
     uint64_t num_seeds;
     uint64_t num_hits;      /* H */
@@ -294,7 +311,10 @@ typedef struct sa_call_stats {
                                2 table-direct with target context (sa_get_lookup_mode) */
     uint32_t path_flags;    /* SA_PATH_*: which of the engine's rare branches the call took (diagnostics; the results never depend on them).
                                Summed statistics (sa_seed_calls, sa_seed_interval) carry the OR over their calls */
-    uint64_t num_forwarded; /* context-table calls: hits the class filter (level 1) handed to the second level; 0 otherwise */
+    uint64_t num_forwarded; /* context-table calls: the records the second level read from the class filter's (level 1's) hand-over list in
+                               the last attempt of every batch -- the 256 sub-list counts, each clamped to the sub-list capacity; exactly the
+                               records sa_get_forwards returns under option fwd_keep, and equal to the number of hits level 1 could not
+                               decide (tests/test_gpu_filter_verdicts.py holds it to a model, hit for hit); 0 otherwise */
 } sa_call_stats;
 #define SA_PATH_LIST_REGROWN 1u          /* a device list (second-level / candidate / entropy / survivor) overflowed: regrown, batch rerun */
 #define SA_PATH_DEDUP_FALLBACK 2u        /* a segment held more survivors than the LDS chain takes: library sorts + unique */

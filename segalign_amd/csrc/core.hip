@@ -31,6 +31,8 @@ size_t saf_core(DevCtx* dc, Slot* sl, uint32_t num_seeds, const CoreArgs& ca, sa
     uint32_t n_final = 0;
     uint32_t survivors = 0;
     uint64_t n_cand_total = 0, n_ent_total = 0, n_fwd_total = 0;
+    bool ran_cls = false;      // a batch of the call went through the class filter and the second level (what option fwd_keep reads back)
+    uint32_t ran_l2_cap = 0;   // ... with this sub-list capacity in its last attempt
     uint32_t path_flags = t_front_flags;  // SA_PATH_* of this call (the front of the call may have set some already)
     t_front_flags = 0;
     // chunks of the seed vector (one for an ordinary call)
@@ -325,6 +327,8 @@ size_t saf_core(DevCtx* dc, Slot* sl, uint32_t num_seeds, const CoreArgs& ca, sa
                                 launch_extend_filter_cls(ea, st);
                             }
                         }
+                        ran_cls = true;
+                        ran_l2_cap = ea.l2_cap;
                         ExtendArgs e2 = ea;
                         e2.td = 0;
                         e2.src_cand = 1;
@@ -422,6 +426,29 @@ size_t saf_core(DevCtx* dc, Slot* sl, uint32_t num_seeds, const CoreArgs& ca, sa
                 if (na) {
                     check_memcpy(hipMemcpyAsync(t_audit.data(), sl->audit.p, (size_t)na * sizeof(uint2), hipMemcpyDeviceToHost, st), "audit");
                     check_sync(st, "audit");
+                }
+            }
+            if (g_fwd_keep && ca.td && dc->nbr_ctx) {  // (tests) what level 1 handed over in the last attempt of the last batch
+                t_forwards.clear();
+                memset(t_fwd_counts, 0, sizeof(t_fwd_counts));
+                if (ran_cls) {  // (the predicate of the launch itself: a call without hits ran no filter and keeps an empty list)
+                    std::vector<uint32_t> raw((size_t)L2_NSUB * L2_CNT_STRIDE);
+                    check_memcpy(hipMemcpyAsync(raw.data(), sl->l2_counts.p, raw.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "forwards");
+                    check_sync(st, "forwards");
+                    const size_t cap = ran_l2_cap;  // (the capacity the last attempt ran with)
+                    size_t total = 0;
+                    for (int s = 0; s < L2_NSUB; s++) {
+                        t_fwd_counts[s] = raw[(size_t)s * L2_CNT_STRIDE];
+                        total += std::min<size_t>(t_fwd_counts[s], cap);
+                    }
+                    t_forwards.resize(total);
+                    size_t at = 0;
+                    for (int s = 0; s < L2_NSUB; s++) {
+                        const size_t n = std::min<size_t>(t_fwd_counts[s], cap);
+                        if (n) check_memcpy(hipMemcpyAsync(t_forwards.data() + at, sl->l2_list.p + (size_t)s * cap, n * sizeof(L2Rec), hipMemcpyDeviceToHost, st), "forwards");
+                        at += n;
+                    }
+                    check_sync(st, "forwards");
                 }
             }
             t_stats.num_examined = sl->h_cnt->examined;

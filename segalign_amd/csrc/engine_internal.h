@@ -501,6 +501,7 @@ extern int64_t g_call_hits, g_call_hits_max;
 extern int g_no_small_dedup;
 extern int g_ctx;
 extern uint32_t g_audit_cap;
+extern int g_fwd_keep;
 extern int g_td;
 extern int g_chain;
 extern uint32_t CHAIN_CAP;
@@ -509,6 +510,8 @@ extern uint32_t g_query_len[SA_BUFFER_DEPTH];
 extern thread_local sa_call_stats t_stats;
 extern thread_local sa_call_trace t_trace;
 extern thread_local std::vector<uint2> t_audit;
+extern thread_local std::vector<L2Rec> t_forwards;
+extern thread_local uint32_t t_fwd_counts[L2_NSUB];
 extern thread_local uint32_t t_front_flags;  // SA_PATH_* bits the front of the calling thread's current call has set (front.hip -> core.hip)
 
 int64_t opt_value(const char* name);  // the option table (options.hip)

@@ -50,6 +50,7 @@ int64_t g_call_hits = 128ll << 20;  // option call_hits: seed hits a call is siz
 int g_chunks_per_call = SA_DEFAULT_CHUNKS;  // SEGALIGN_AMD_CHUNKS_PER_CALL: chunks sa_seed_interval hands to one multi-chunk call
 int g_no_small_dedup = 0;  // SEGALIGN_AMD_NO_SMALL_DEDUP=1: always use the library sorts
 int g_ctx = 1;             // neighbourhood table with target context when it fits (SEGALIGN_AMD_NO_CTX=1: positions only)
+int g_fwd_keep = 0;        // option fwd_keep (tests): keep the hand-over list of a context-table call (sa_get_forwards)
 uint32_t g_audit_cap = 0;  // SEGALIGN_AMD_AUDIT_CAP (tests): record up to this many hits the filter levels reject per call
 int g_td = 1;              // table-direct lookup (neighbourhood table + position probe, probe.hip); SEGALIGN_AMD_NO_TD=1 turns it off
 int g_chain = 1;           // chain shortcut of the exact stage (SEGALIGN_AMD_NO_CHAIN=1 turns it off)
@@ -60,6 +61,8 @@ uint32_t g_query_len[SA_BUFFER_DEPTH] = {0, 0};
 thread_local sa_call_stats t_stats;
 thread_local sa_call_trace t_trace;  // which branches of saf_core the calling thread's last call took (sa_get_last_call_trace)
 thread_local std::vector<uint2> t_audit;
+thread_local std::vector<L2Rec> t_forwards;   // (option fwd_keep) the hand-over list of the calling thread's last context-table call
+thread_local uint32_t t_fwd_counts[L2_NSUB];  // ... and its raw sub-list counters
 thread_local uint32_t t_front_flags = 0;  // rejected hits of the calling thread's last hot call (audit option)
 uint32_t SPEC_RECS = 16384;
 uint32_t g_dedup_seg_max = 0;
@@ -156,6 +159,7 @@ static Option g_opts[] = {
     {"cand_cap", 0, 0, 1 << 30, 1}, {"ent_cap", 0, 0, 1 << 30, 1}, {"out_cap", 0, 0, 1 << 26, 1},  // first size of the candidate / entropy / survivor list of a batch (0: sized by the hits); saf_core's rerun loop regrows them
     {"hit_batch", 0, 0, 1ll << 40, 1},                 // hits per extension batch of the general path (0: 2^27)
     {"no_small_dedup", 0, 0, 1, 1}, {"chain_no_link", 0, 0, 1, 1}, {"chain_cap", 1 << 23, 1, 1 << 30, 1}, {"audit_cap", 0, 0, 1 << 28, 1},
+    {"fwd_keep", 0, 0, 1, 1},                          // (tests) 1: a context-table call reads the class filter's hand-over list back for sa_get_forwards
 };
 static Option* find_option(const char* name) {
     for (auto& o : g_opts)
@@ -238,6 +242,7 @@ void resolve_options() {
     g_no_small_dedup = (int)opt_value("no_small_dedup");
     CHAIN_CAP = (uint32_t)opt_value("chain_cap");
     g_audit_cap = (uint32_t)opt_value("audit_cap");
+    g_fwd_keep = (int)opt_value("fwd_keep");
     g_q2_limit = (size_t)opt_value("q2_limit_mb") << 20;
     g_q2_copies = opt_value("cls_one_copy") == 2 ? Q2_COPIES : 1;
 }
@@ -312,6 +317,14 @@ size_t sa_get_audit(uint32_t* dst_pairs, size_t cap_pairs) {
     const size_t n = std::min(cap_pairs, t_audit.size());
     if (n) memcpy(dst_pairs, t_audit.data(), n * sizeof(uint2));
     return t_audit.size();
+}
+// (tests, option fwd_keep) the records the class filter handed to the second level in the calling thread's last context-table call,
+// concatenated in sub-list order (L2Rec, 20 bytes each), and the 256 raw sub-list counters; returns how many records were kept
+size_t sa_get_forwards(void* dst_l2recs, size_t cap_recs, uint32_t* sub_counts256) {
+    const size_t n = std::min(cap_recs, t_forwards.size());
+    if (n) memcpy(dst_l2recs, t_forwards.data(), n * sizeof(L2Rec));
+    if (sub_counts256) memcpy(sub_counts256, t_fwd_counts, sizeof(t_fwd_counts));
+    return t_forwards.size();
 }
 int sa_max_hits_for_mem(uint64_t total_global_mem) { return max_hits_for_mem(total_global_mem); }
 

@@ -41,7 +41,7 @@ C_ABI_SYMBOLS = [
     "sa_get_table_build_info", "sa_copy_neighbourhood_starts", "sa_copy_neighbourhood_records",
     "sa_probe_call", "sa_free_probe_call",
     "sa_copy_image", "sa_get_code_presence", "sa_get_class_scores",
-    "sa_seed_calls", "sa_count_call_hits", "sa_count_chunk_hits", "sa_get_wga_chunk", "sa_release_arena", "sa_set_option", "sa_reset_option", "sa_get_option", "sa_option_count", "sa_option_name", "sa_get_audit",
+    "sa_seed_calls", "sa_count_call_hits", "sa_count_chunk_hits", "sa_get_wga_chunk", "sa_release_arena", "sa_set_option", "sa_reset_option", "sa_get_option", "sa_option_count", "sa_option_name", "sa_get_audit", "sa_get_forwards",
     "sa_gapped_extend", "sa_free_gapped", "sa_gapped_align", "sa_free_gapped_align", "sa_gapped_align_greedy",
     "sa_chain_hsps", "sa_free_chain", "sa_chain_hsps_all", "sa_free_chain_all",
     "sa_chain_hsps_costs", "sa_chain_hsps_all_costs", "sa_chain_gap_preset",
@@ -394,6 +394,8 @@ def lib():
     L.sa_option_name.argtypes = [C.c_int, C.POINTER(C.c_int)]
     L.sa_get_audit.restype = C.c_size_t
     L.sa_get_audit.argtypes = [C.c_void_p, C.c_size_t]
+    L.sa_get_forwards.restype = C.c_size_t
+    L.sa_get_forwards.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
     L.sa_gapped_extend.restype = C.c_size_t
     L.sa_gapped_extend.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(GappedParams), C.c_int, C.POINTER(C.c_void_p),
                                    C.POINTER(GappedStats)]
@@ -1395,3 +1397,16 @@ def get_audit(cap=1 << 22):
     buf = np.empty((cap, 2), dtype=np.uint32)
     n = lib().sa_get_audit(buf.ctypes.data, cap)
     return buf[:min(n, cap)].copy(), int(n)
+
+
+L2REC_DTYPE = np.dtype([("ref_loc", "<u4"), ("query_loc", "<u4"), ("hidx", "<u4"), ("state", "<u4"), ("meta", "<u4")])
+
+
+def get_forwards(cap=1 << 22):
+    """(records, total, sub_counts) of the hand-over list of this thread's last context-table call (option fwd_keep): the records the
+    class filter gave the second level, in sub-list order (sa_get_forwards documents the 20-byte record), how many the call kept,
+    and the 256 raw sub-list counters."""
+    buf = np.empty(cap, dtype=L2REC_DTYPE)
+    counts = np.zeros(256, dtype=np.uint32)
+    n = lib().sa_get_forwards(buf.ctypes.data, cap, counts.ctypes.data)
+    return buf[:min(n, cap)].copy(), int(n), counts
