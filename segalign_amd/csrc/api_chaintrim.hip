@@ -9,24 +9,7 @@ using namespace sa;
 
 namespace {
 
-void fail(const char* fmt, long long a = 0, long long b = 0) {
-    fprintf(stderr, "Error: TrimChains: ");
-    fprintf(stderr, fmt, a, b);
-    fprintf(stderr, "\n");
-    exit(1);
-}
-
-// The checks of the chain list (those of sa_stitch_chains); returns the number of member entries.
-size_t checked_first(const uint32_t* first, size_t n_chains) {
-    if (n_chains > (1u << 22)) fail("%lld chains: at most 1 << 22", (long long)n_chains);
-    if (n_chains == 0) return 0;
-    if (first[0] != 0) fail("first[0] = %lld, not 0", first[0]);
-    for (size_t c = 0; c < n_chains; c++)
-        if (first[c + 1] < first[c]) fail("first[] decreases at chain %lld", (long long)c);
-    const size_t M = first[n_chains];
-    if (M > (1u << 22)) fail("%lld members: at most 1 << 22", (long long)M);
-    return M;
-}
+const Fail fail{"TrimChains"};
 
 }  // namespace
 
@@ -52,7 +35,7 @@ size_t sa_trim_chains(const sa_segment_pair* hsps, size_t n_hsps, const uint32_t
     if ((flags & SA_TRIM_LINKS) && (!links || !n_links)) fail("SA_TRIM_LINKS needs links and n_links");
     CostImage costs;
     checked_costs(who, g, costs);
-    const size_t M = checked_first(first, n_chains);
+    const size_t M = checked_first(fail, first, n_chains);
     if (M == 0) return 0;
 
     Slot* sl = acquire_slot();
@@ -62,13 +45,7 @@ size_t sa_trim_chains(const sa_segment_pair* hsps, size_t n_hsps, const uint32_t
 
     // the members, each inside the block; out starts as the input HSPs, so that an untouched member is returned bit for bit
     std::vector<sa_segment_pair> out(M);
-    for (size_t k = 0; k < M; k++) {
-        if (members[k] >= n_hsps) fail("member %lld names HSP %lld, which is not in the input", (long long)k, members[k]);
-        const sa_segment_pair& h = hsps[members[k]];
-        if ((uint64_t)h.ref_start + h.len + 1 > a.ref_len || (uint64_t)h.query_start + h.len + 1 > a.query_len)
-            fail("member %lld (HSP %lld) does not lie inside the block", (long long)k, members[k]);
-        out[k] = h;
-    }
+    for (size_t k = 0; k < M; k++) out[k] = checked_member(fail, hsps, n_hsps, members, k, a.ref_len, a.query_len);
     // the links in entry order: overlap, gaps between the trimmed members, and a crossover task where o > 0
     std::vector<sa_trim_link> lk;
     std::vector<size_t> lk_entry;  // the entry of the link's first member
@@ -100,12 +77,12 @@ size_t sa_trim_chains(const sa_segment_pair* hsps, size_t n_hsps, const uint32_t
         TrimLinkTask* d_tasks;
         uint32_t* d_x;
         carve(sl->stitch, "trim", [&](Carve& c) { c.take(d_tasks, T).take(d_x, T); });
-        check_memcpy(hipMemcpyAsync(d_tasks, tasks.data(), T * sizeof(TrimLinkTask), hipMemcpyHostToDevice, s), "trim tasks");
+        to_device(d_tasks, tasks.data(), T, s, "trim tasks");
         tm.mark(0);
         launch(sl, "chaintrim_crossover", [&] { launch_chaintrim_crossover(a, d_tasks, (uint32_t)T, d_x, s); });
         tm.mark(1);
         std::vector<uint32_t> x(T);
-        check_memcpy(hipMemcpyAsync(x.data(), d_x, T * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "trim crossovers");
+        to_host(x.data(), d_x, T, s, "trim crossovers");
         check_sync(s, "chaintrim_crossover");
         st.kernel_ms += tm.ms(0, 1);
         // cut the members: j loses its last o - x columns, i its first x; o1 + o2 < bases leaves every member a base
@@ -139,12 +116,12 @@ size_t sa_trim_chains(const sa_segment_pair* hsps, size_t n_hsps, const uint32_t
         StitchMember* d_mem;
         StitchMemberOut* d_mo;
         carve(sl->stitch, "trim", [&](Carve& c) { c.take(d_mem, K).take(d_mo, K); });
-        check_memcpy(hipMemcpyAsync(d_mem, cut.data(), K * sizeof(StitchMember), hipMemcpyHostToDevice, s), "trim members");
+        to_device(d_mem, cut.data(), K, s, "trim members");
         tm.mark(2);
         launch(sl, "chaintrim_rescore", [&] { launch_stitch_members(a, d_mem, (uint32_t)K, d_mo, s); });
         tm.mark(3);
         std::vector<StitchMemberOut> mo(K);
-        check_memcpy(hipMemcpyAsync(mo.data(), d_mo, K * sizeof(StitchMemberOut), hipMemcpyDeviceToHost, s), "trim member scores");
+        to_host(mo.data(), d_mo, K, s, "trim member scores");
         check_sync(s, "chaintrim_rescore");
         st.kernel_ms += tm.ms(2, 3);
         for (size_t k = 0; k < K; k++) {

@@ -10,12 +10,7 @@ using namespace sa;
 
 namespace {
 
-void fail(const char* fmt, long long a = 0, long long b = 0) {
-    fprintf(stderr, "Error: FillChains: ");
-    fprintf(stderr, fmt, a, b);
-    fprintf(stderr, "\n");
-    exit(1);
-}
+const Fail fail{"FillChains"};
 
 struct Params {
     int32_t thresh, xdrop;
@@ -45,18 +40,6 @@ Params resolve(const sa_fill_params* fp) {
     // a diagonal has at most max_side cells, so |s| <= max_side A
     if ((long long)r.max_side * A >= (1ll << 31)) fail("max_side = %lld leaves no int32 headroom (max_side * %lld >= 1 << 31)", r.max_side, A);
     return r;
-}
-
-// The checks of the chain list (those of sa_stitch_chains); returns the number of member entries.
-size_t checked_first(const uint32_t* first, size_t n_chains) {
-    if (n_chains > (1u << 22)) fail("%lld chains: at most 1 << 22", (long long)n_chains);
-    if (n_chains == 0) return 0;
-    if (first[0] != 0) fail("first[0] = %lld, not 0", first[0]);
-    for (size_t c = 0; c < n_chains; c++)
-        if (first[c + 1] < first[c]) fail("first[] decreases at chain %lld", (long long)c);
-    const size_t M = first[n_chains];
-    if (M > (1u << 22)) fail("%lld members: at most 1 << 22", (long long)M);
-    return M;
 }
 
 struct Origin {  // a link's rectangle
@@ -105,8 +88,8 @@ void sweep(Slot* sl, const StitchArgs& a, const Params& P, std::vector<sa_fill_l
             c.take(d_tasks, T).take(d_cnt, (size_t)n + 1).take(d_off, (size_t)n + 1).take(d_at, nl + 1).take(d_loff, nl + 1);
             c.take(temp, temp_bytes).take(d_out, cap).take(d_olink, cap);
         });
-        check_memcpy(hipMemcpyAsync(d_tasks, tasks.data(), T * sizeof(FillTask), hipMemcpyHostToDevice, s), "fill tasks");
-        check_memcpy(hipMemcpyAsync(d_at, at.data(), (nl + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s), "fill links");
+        to_device(d_tasks, tasks.data(), T, s, "fill tasks");
+        to_device(d_at, at.data(), nl + 1, s, "fill links");
         check_memcpy(hipMemsetAsync(d_cnt + n, 0, sizeof(uint32_t), s), "fill counts");  // the prefix sum reads n + 1 entries
         tm.mark(0);
         launch(sl, "fill_count", [&] {
@@ -116,7 +99,7 @@ void sweep(Slot* sl, const StitchArgs& a, const Params& P, std::vector<sa_fill_l
         });
         tm.mark(1);
         loff.resize(nl + 1);
-        check_memcpy(hipMemcpyAsync(loff.data(), d_loff, (nl + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s), "fill offsets");
+        to_host(loff.data(), d_loff, nl + 1, s, "fill offsets");
         check_sync(s, "fill_count");
         st.count_ms += tm.ms(0, 1);
         for (size_t k = 0; k < nl; k++) {
@@ -140,8 +123,8 @@ void sweep(Slot* sl, const StitchArgs& a, const Params& P, std::vector<sa_fill_l
                 tm.mark(3);
                 h_out.resize(H);
                 h_link.resize(H);
-                check_memcpy(hipMemcpyAsync(h_out.data(), d_out, H * sizeof(sa_segment_pair), hipMemcpyDeviceToHost, s), "fill HSPs");
-                check_memcpy(hipMemcpyAsync(h_link.data(), d_olink, H * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "fill HSP links");
+                to_host(h_out.data(), d_out, H, s, "fill HSPs");
+                to_host(h_link.data(), d_olink, H, s, "fill HSP links");
                 check_sync(s, "fill_emit");
                 st.emit_ms += tm.ms(2, 3);
                 if (found.size() + H >= 0xFFFFFFFFull) fail("more than 2^32 - 1 HSPs found: raise thresh");
@@ -186,7 +169,7 @@ size_t sa_fill_chains(const sa_segment_pair* hsps, size_t n_hsps, const uint32_t
     if ((flags & SA_FILL_HSPS) && (!found_out || !n_found)) fail("SA_FILL_HSPS needs found and n_found");
     CostImage costs;
     checked_costs(who, g, costs);
-    const size_t M = checked_first(first, n_chains);
+    const size_t M = checked_first(fail, first, n_chains);
     if (n_chains == 0) return 0;
 
     std::vector<sa_fill_link> lk;
@@ -196,12 +179,7 @@ size_t sa_fill_chains(const sa_segment_pair* hsps, size_t n_hsps, const uint32_t
         Slot* sl = acquire_slot();
         StitchArgs a;
         resident_block(who, sl, rev, buffer, a);
-        for (size_t k = 0; k < M; k++) {
-            if (members[k] >= n_hsps) fail("member %lld names HSP %lld, which is not in the input", (long long)k, members[k]);
-            const sa_segment_pair& h = hsps[members[k]];
-            if ((uint64_t)h.ref_start + h.len + 1 > a.ref_len || (uint64_t)h.query_start + h.len + 1 > a.query_len)
-                fail("member %lld (HSP %lld) does not lie inside the block", (long long)k, members[k]);
-        }
+        for (size_t k = 0; k < M; k++) checked_member(fail, hsps, n_hsps, members, k, a.ref_len, a.query_len);
         std::vector<size_t> sw;
         for (size_t c = 0; c < n_chains; c++)
             for (size_t k = first[c]; k + 1 < first[c + 1]; k++) {

@@ -105,12 +105,12 @@ std::vector<GappedSide> extend_sides(Frame& f, const sa_segment_pair* hsps, size
     a.out = d_side;
     for (size_t b = 0; b < n; b += batch) {
         const size_t m = std::min(batch, n - b);
-        check_memcpy(hipMemcpyAsync(d_hsps, hsps + b, m * sizeof(sa_segment_pair), hipMemcpyHostToDevice, sl->stream), "gapped hsps");
+        to_device(d_hsps, hsps + b, m, sl->stream, "gapped hsps");
         a.num_tasks = (uint32_t)(2 * m);
         tm.mark(0);
         launch(sl, "gapped_extend", [&] { launch_gapped(a, sl->stream); });
         tm.mark(1);
-        check_memcpy(hipMemcpyAsync(side.data() + 2 * b, d_side, 2 * m * sizeof(GappedSide), hipMemcpyDeviceToHost, sl->stream), "gapped results");
+        to_host(side.data() + 2 * b, d_side, 2 * m, sl->stream, "gapped results");
         check_sync(sl->stream, "gapped_extend");
         st.kernel_ms += tm.ms(0, 1);
     }
@@ -161,11 +161,11 @@ void continue_sides(Frame& f, const sa_segment_pair* hsps, Sides& S, sa_gapped_s
         for (size_t k = 0; k < m; k++) tasks[k] = open[k].t;
         for (size_t b = 0; b < m; b += batch) {
             const size_t c = std::min(batch, m - b);
-            check_memcpy(hipMemcpyAsync(d_tasks, tasks.data() + b, c * sizeof(SideTask), hipMemcpyHostToDevice, sl->stream), "gapped pieces");
+            to_device(d_tasks, tasks.data() + b, c, sl->stream, "gapped pieces");
             tm.mark(0);
             launch(sl, "gapped_pieces", [&] { launch_gapped_sides(f.a, d_tasks, (uint32_t)c, d_side, sl->stream); });
             tm.mark(1);
-            check_memcpy(hipMemcpyAsync(res.data() + b, d_side, c * sizeof(GappedSide), hipMemcpyDeviceToHost, sl->stream), "gapped pieces");
+            to_host(res.data() + b, d_side, c, sl->stream, "gapped pieces");
             check_sync(sl->stream, "gapped_pieces");
             st.kernel_ms += tm.ms(0, 1);
         }
@@ -308,15 +308,15 @@ void trace_sides(Frame& f, Traces& tr, sa_gapped_align_stats& st, const TraceHoo
         uint32_t* d_ops;
         uint8_t* d_area;
         carve(sl->gapped_trace, "gapped trace", [&](Carve& c) { c.take(d_tasks, m).take(d_out, m).take(d_ops, bt.nops).take(d_area, bt.trace); });
-        check_memcpy(hipMemcpyAsync(d_tasks, bt.tasks.data(), m * sizeof(TraceTask), hipMemcpyHostToDevice, sl->stream), "gapped trace tasks");
+        to_device(d_tasks, bt.tasks.data(), m, sl->stream, "gapped trace tasks");
         tm.mark(0);
         launch(sl, "gapped_trace", [&] { launch_gapped_trace(f.a, d_tasks, (uint32_t)m, d_area, sl->stream); });
         tm.mark(1);
         launch(sl, "gapped_walk", [&] { launch_gapped_walk(f.a, d_tasks, (uint32_t)m, d_area, d_ops, d_out, sl->stream); });
         tm.mark(2);
         bops.resize(bt.nops);
-        check_memcpy(hipMemcpyAsync(tr.res.data() + b, d_out, m * sizeof(TraceOut), hipMemcpyDeviceToHost, sl->stream), "gapped walk results");
-        check_memcpy(hipMemcpyAsync(bops.data(), d_ops, bt.nops * sizeof(uint32_t), hipMemcpyDeviceToHost, sl->stream), "gapped ops");
+        to_host(tr.res.data() + b, d_out, m, sl->stream, "gapped walk results");
+        to_host(bops.data(), d_ops, bt.nops, sl->stream, "gapped ops");
         check_sync(sl->stream, "gapped_align");
         st.trace_ms += tm.ms(0, 1);
         st.walk_ms += tm.ms(1, 2);
@@ -425,7 +425,7 @@ struct CoverIndex {
     // covered[k] = 1 when the point key keys[k] lies on the index (R > 0); d_cov: n bytes on the device
     void query(const uint64_t* keys, size_t n, uint8_t* d_cov, uint8_t* covered) {
         group("cover_query", [&] { launch_cover_query(sl->cover_key[cur].p, sl->cover_run[cur].p, R, keys, (uint32_t)n, d_cov, sl->stream); });
-        check_memcpy(hipMemcpyAsync(covered, d_cov, n, hipMemcpyDeviceToHost, sl->stream), "cover query");
+        to_host(covered, d_cov, n, sl->stream, "cover query");
         check_sync(sl->stream, "cover_query");
     }
     // the M selected segments in w.sk / w.sdt merged into the index, written to the other buffer of the pair
@@ -450,7 +450,7 @@ std::vector<uint32_t> survivors(Frame& f, CoverIndex& ix, const sa_segment_pair*
     uint64_t* d_qk;
     uint8_t* d_cov;
     carve(f.sl->cover_work, "cover work", [&](Carve& c) { c.take(d_qk, m).take(d_cov, m); });
-    check_memcpy(hipMemcpyAsync(d_qk, qk.data(), m * 8, hipMemcpyHostToDevice, f.sl->stream), "cover query keys");
+    to_device(d_qk, qk.data(), m, f.sl->stream, "cover query keys");
     std::vector<uint8_t> cov(m);
     ix.query(d_qk, m, d_cov, cov.data());
     std::vector<uint32_t> surv;
@@ -475,7 +475,7 @@ size_t trace_emit(Frame& f, CoverIndex& ix, Traces& tr, sa_gapped_align_stats& s
         }
         sl->cover_segs.ensure((nseg + add) * sizeof(CoverSeg), "cover segments", true, sl->stream);
         sl->cover_work.ensure(cnt * sizeof(CoverEmit), "cover work");
-        check_memcpy(hipMemcpyAsync(sl->cover_work.p, em.data(), cnt * sizeof(CoverEmit), hipMemcpyHostToDevice, sl->stream), "cover emit");
+        to_device((CoverEmit*)sl->cover_work.p, em.data(), cnt, sl->stream, "cover emit");
         ix.group("cover_emit", [&] {
             launch_cover_emit(d_tasks, d_out, d_ops, (const CoverEmit*)sl->cover_work.p, (uint32_t)cnt, f.a.query_len,
                               (CoverSeg*)sl->cover_segs.p, sl->stream);
@@ -511,9 +511,7 @@ CoverWork cover_work(Frame& f, CoverIndex& ix, const std::vector<sa_segment_pair
         if (elig[r]) unit.push_back({akey[r], a.t + 1, (uint32_t)r});
     }
     sl->cover_segs.ensure((nseg + unit.size()) * sizeof(CoverSeg), "cover segments", true, s);
-    if (!unit.empty())
-        check_memcpy(hipMemcpyAsync((CoverSeg*)sl->cover_segs.p + nseg, unit.data(), unit.size() * sizeof(CoverSeg), hipMemcpyHostToDevice, s),
-                     "cover anchor segments");
+    to_device((CoverSeg*)sl->cover_segs.p + nseg, unit.data(), unit.size(), s, "cover anchor segments");
     nseg += unit.size();
     if (nseg > 0xffffffffull) {
         fprintf(stderr, "Error: GappedAlignGreedy: %zu cover segments in one batch\n", nseg);
@@ -530,8 +528,8 @@ CoverWork cover_work(Frame& f, CoverIndex& ix, const std::vector<sa_segment_pair
     w.temp = sl->cover_temp.p;
     w.temp_cap = sl->cover_temp.cap;
     w.nseg = nseg;
-    check_memcpy(hipMemcpyAsync(w.akin, akey.data(), S * 8, hipMemcpyHostToDevice, s), "cover anchors");
-    check_memcpy(hipMemcpyAsync(w.rin, arank.data(), S * 4, hipMemcpyHostToDevice, s), "cover anchors");
+    to_device(w.akin, akey.data(), S, s, "cover anchors");
+    to_device(w.rin, arank.data(), S, s, "cover anchors");
     hipMemsetAsync(w.state, 0, S, s);
     ix.group("cover_edges", [&] { cover_sort_anchors(w.temp, w.tbytes(), w.akin, w.akey, w.rin, w.rank, (uint32_t)S, s); });
     return w;
@@ -557,20 +555,20 @@ std::vector<uint8_t> resolve_passes(CoverIndex& ix, CoverWork& w, std::vector<ui
             for (size_t r = lo; r < S; r++)
                 if (pre[r]) el[r] = 0;  // covered by an accepted survivor of an earlier pass: final, never accepted, no edges
         }
-        check_memcpy(hipMemcpyAsync(w.elig + lo, el.data() + lo, nr, hipMemcpyHostToDevice, s), "cover eligible");
+        to_device(w.elig + lo, el.data() + lo, nr, s, "cover eligible");
         uint64_t total = 0;
         ix.group("cover_edges", [&] {
             hipMemsetAsync(w.deg, 0, (nr + 1) * 4, s);
             launch_cover_edges(d_segs, (uint32_t)w.nseg, w.akey, w.rank, (uint32_t)S, w.elig, (uint32_t)lo, (uint32_t)S, w.deg, nullptr, nullptr, 1, s);
             cover_scan_offsets(w.temp, w.tbytes(), w.deg, w.row, (uint32_t)nr, s);
         });
-        check_memcpy(hipMemcpyAsync(&total, w.row + nr, 8, hipMemcpyDeviceToHost, s), "cover edges");
+        to_host(&total, w.row + nr, 1, s, "cover edges");
         check_sync(s, "cover_edges");
         size_t hi = S;
         uint64_t n_edges = total;
         if (total > cap) {  // the longest prefix of ranks whose edges fit, at least one survivor
             row_h.resize(nr + 1);
-            check_memcpy(hipMemcpyAsync(row_h.data(), w.row, (nr + 1) * 8, hipMemcpyDeviceToHost, s), "cover edges");
+            to_host(row_h.data(), w.row, nr + 1, s, "cover edges");
             check_sync(s, "cover_edges");
             size_t k = (size_t)(std::upper_bound(row_h.begin(), row_h.end(), cap) - row_h.begin()) - 1;
             if (k < 1) k = 1;
@@ -588,8 +586,8 @@ std::vector<uint8_t> resolve_passes(CoverIndex& ix, CoverWork& w, std::vector<ui
             launch_cover_select(d_segs, (uint32_t)w.nseg, w.state, (uint32_t)lo, (uint32_t)hi, w.sk, w.sdt, w.cnt, s);
         });
         uint32_t M = 0;
-        check_memcpy(hipMemcpyAsync(state.data() + lo, w.state + lo, nh, hipMemcpyDeviceToHost, s), "cover resolve");
-        check_memcpy(hipMemcpyAsync(&M, w.cnt, 4, hipMemcpyDeviceToHost, s), "cover resolve");
+        to_host(state.data() + lo, w.state + lo, nh, s, "cover resolve");
+        to_host(&M, w.cnt, 1, s, "cover resolve");
         check_sync(s, "cover_resolve");
         if (M > 0) ix.merge(w, M);
         for (size_t r = lo; r < hi; r++)

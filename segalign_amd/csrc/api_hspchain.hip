@@ -62,7 +62,6 @@ void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, u
         c.take(d.d_members, N).take(d.d_nodes, N).take(d_image, HSPCOST_WORDS);
         if (max_overlap) c.take(ovl_w, N).take(ovl_lim, N);
     });
-    if (!group) d_group = nullptr;
     sl->hspchain_partial.ensure((size_t)tiles * T * sizeof(HspChainPartial), "hsp chain partials");
     HspChainPartial* partial = (HspChainPartial*)sl->hspchain_partial.p;
     size_t sort_bytes = 0, scan_bytes = 0;
@@ -81,8 +80,8 @@ void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, u
     a.max_gap = d.P.max_gap;
     const uint32_t* image = costs.on ? d_image : nullptr;  // picks the DP's instances, and the scope names they are profiled under
 
-    check_memcpy(hipMemcpyAsync(d_hsps, hsps, n * sizeof(sa_segment_pair), hipMemcpyHostToDevice, s), "hsp chain: HSPs");
-    if (group) check_memcpy(hipMemcpyAsync(d_group, group, n * sizeof(uint32_t), hipMemcpyHostToDevice, s), "hsp chain: groups");
+    to_device(d_hsps, hsps, n, s, "hsp chain: HSPs");
+    d_group = upload(d_group, group, n, s, "hsp chain: groups");
     if (costs.on) check_memcpy(hipMemcpyAsync(d_image, costs.w, sizeof(costs.w), hipMemcpyHostToDevice, s), "hsp chain: gap costs");
 
     // rank: stable sort by (query_start, len) with the input index as value, then by (group, ref_start); idx_a ends up as rank -> input index
@@ -98,7 +97,7 @@ void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, u
         if (max_overlap) launch_hspovl_weight(a, max_overlap, ovl_w, ovl_lim, s);
     });
     ev.mark(1);
-    check_memcpy(hipMemcpyAsync(h_first.data(), first, tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "hsp chain: first tiles");
+    to_host(h_first.data(), first, tiles, s, "hsp chain: first tiles");
     check_sync(s, "hspchain_rank");
     d.order = idx_a;
 
@@ -128,7 +127,7 @@ void rank_and_dp(const sa_segment_pair* hsps, size_t n, const uint32_t* group, u
     cover_scan_offsets(temp, &d.temp_bytes, d.head, d.gidx, N, s);
     ev.mark(3);
     uint64_t groups64 = 0;
-    check_memcpy(hipMemcpyAsync(&groups64, d.gidx + N, sizeof(uint64_t), hipMemcpyDeviceToHost, s), "hsp chain: groups");
+    to_host(&groups64, d.gidx + N, 1, s, "hsp chain: groups");
     check_sync(s, "hspchain tiles");
     d.G = (uint32_t)groups64;
 }
@@ -181,7 +180,7 @@ size_t chain_hsps(const sa_segment_pair* hsps, size_t n, const uint32_t* group, 
     });
     ev.mark(5);
     uint64_t total = 0;
-    check_memcpy(hipMemcpyAsync(&total, d.goff + G, sizeof(uint64_t), hipMemcpyDeviceToHost, s), "hsp chain: members");
+    to_host(&total, d.goff + G, 1, s, "hsp chain: members");
     check_sync(s, "hspchain_finish");
     ev.mark(6);
     launch(sl, "hspchain_finish", [&] {
@@ -191,8 +190,8 @@ size_t chain_hsps(const sa_segment_pair* hsps, size_t n, const uint32_t* group, 
     ev.mark(7);
     sa_chain_member* m_out = host_alloc<sa_chain_member>(total, "ChainHsps");
     sa_chain_node* n_out = nodes ? host_alloc<sa_chain_node>(n, "ChainHsps") : nullptr;
-    if (total) check_memcpy(hipMemcpyAsync(m_out, d.d_members, total * sizeof(sa_chain_member), hipMemcpyDeviceToHost, s), "hsp chain: members");
-    if (nodes) check_memcpy(hipMemcpyAsync(n_out, d.d_nodes, n * sizeof(sa_chain_node), hipMemcpyDeviceToHost, s), "hsp chain: nodes");
+    to_host(m_out, d.d_members, total, s, "hsp chain: members");
+    if (nodes) to_host(n_out, d.d_nodes, n, s, "hsp chain: nodes");
     check_sync(s, "hspchain_finish");
     st.kernel_ms = ev.ms(0, 1) + ev.ms(2, 3) + ev.ms(4, 5) + ev.ms(6, 7);
     prof_flush(sl);
@@ -281,7 +280,7 @@ size_t chain_hsps_all(const sa_segment_pair* hsps, size_t n, const uint32_t* gro
     });
     ev.mark(7);
     uint64_t tot[3] = {0, 0, 0};
-    check_memcpy(hipMemcpyAsync(tot, a.tot, sizeof(tot), hipMemcpyDeviceToHost, s), "hsp peel: totals");
+    to_host(tot, a.tot, 3, s, "hsp peel: totals");
     check_sync(s, "hsppeel");
     const size_t K = (size_t)tot[0], M = (size_t)tot[1];
     if (K > n || M > n || K > M || tot[2] < K || tot[2] > n) {
@@ -293,10 +292,10 @@ size_t chain_hsps_all(const sa_segment_pair* hsps, size_t n, const uint32_t* gro
     sa_chain_all_member* m_out = host_alloc<sa_chain_all_member>(M, "ChainHsps");
     sa_chain_node* n_out = nodes ? host_alloc<sa_chain_node>(n, "ChainHsps") : nullptr;
     uint32_t* o_out = chain_of ? host_alloc<uint32_t>(n, "ChainHsps") : nullptr;
-    if (K) check_memcpy(hipMemcpyAsync(c_out, a.chains, K * sizeof(sa_chain_record), hipMemcpyDeviceToHost, s), "hsp peel: chains");
-    if (M) check_memcpy(hipMemcpyAsync(m_out, a.members, M * sizeof(sa_chain_all_member), hipMemcpyDeviceToHost, s), "hsp peel: members");
-    if (nodes) check_memcpy(hipMemcpyAsync(n_out, d.d_nodes, n * sizeof(sa_chain_node), hipMemcpyDeviceToHost, s), "hsp peel: nodes");
-    if (chain_of) check_memcpy(hipMemcpyAsync(o_out, a.chain_of, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "hsp peel: chain_of");
+    to_host(c_out, a.chains, K, s, "hsp peel: chains");
+    to_host(m_out, a.members, M, s, "hsp peel: members");
+    if (nodes) to_host(n_out, d.d_nodes, n, s, "hsp peel: nodes");
+    if (chain_of) to_host(o_out, a.chain_of, n, s, "hsp peel: chain_of");
     check_sync(s, "hsppeel");
     st.chain.kernel_ms = ev.ms(0, 1) + ev.ms(2, 3);
     st.peel_ms = ev.ms(4, 5) + ev.ms(5, 6) + ev.ms(6, 7);

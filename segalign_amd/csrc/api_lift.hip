@@ -11,53 +11,9 @@ using namespace sa;
 namespace {
 
 const char* const WHO = "LiftIntervals";
-
-void fail(const char* fmt, long long a = 0, long long b = 0) {
-    fprintf(stderr, "Error: LiftIntervals: ");
-    fprintf(stderr, fmt, a, b);
-    fprintf(stderr, "\n");
-    exit(1);
-}
-
-// The CSR and block rules of sa_net_chains and the rules of the other axis (those of sa_net_classify), in one pass.  Returns the
-// number of blocks.
-uint32_t checked_blocks(const uint32_t* first, const uint32_t* bs, const uint32_t* be, const uint32_t* obs, const uint32_t* obe,
-                        const uint8_t* ostrand, size_t n) {
-    if (n > LIFT_MAX_CHAINS) fail("%lld chains: at most 1 << 22", (long long)n);
-    if (n == 0) return 0;
-    if (first[0] != 0) fail("first[0] = %lld, not 0", first[0]);
-    for (size_t c = 0; c < n; c++) {
-        if (first[c + 1] < first[c]) fail("first[] decreases at chain %lld", (long long)c);
-        if (first[c + 1] > LIFT_MAX_BLOCKS) fail("%lld blocks: at most 1 << 26", first[c + 1]);
-        const uint32_t strand = ostrand ? ostrand[c] : 0;
-        if (strand > 1) fail("ostrand[%lld] = %lld: 0 or 1", (long long)c, strand);
-        for (size_t k = first[c]; k < first[c + 1]; k++) {
-            if (bs[k] >= be[k]) fail("chain %lld, block %lld: start >= end", (long long)c, (long long)k);
-            if (be[k] >= LIFT_TOP) fail("chain %lld, block %lld ends at or past 2^31", (long long)c, (long long)k);
-            if (k > first[c] && be[k - 1] > bs[k]) fail("chain %lld: its blocks overlap or descend at block %lld", (long long)c, (long long)k);
-            if (obs[k] >= obe[k]) fail("chain %lld, block %lld: start >= end on the other axis", (long long)c, (long long)k);
-            if (obe[k] >= LIFT_TOP) fail("chain %lld, block %lld ends at or past 2^31 on the other axis", (long long)c, (long long)k);
-            if (obe[k] - obs[k] != be[k] - bs[k]) fail("chain %lld, block %lld: the lengths on the two axes differ", (long long)c, (long long)k);
-            if (k > first[c] && (strand ? obe[k] > obs[k - 1] : obe[k - 1] > obs[k]))
-                fail(strand ? "chain %lld (ostrand 1): its other blocks overlap or ascend at block %lld"
-                            : "chain %lld (ostrand 0): its other blocks overlap or descend at block %lld",
-                     (long long)c, (long long)k);
-        }
-    }
-    return first[n];
-}
-
-template <typename T>
-void to_device(T* dst, const T* src, size_t n, hipStream_t s, const char* tag) {
-    if (n) check_memcpy(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, s), tag);
-}
-
-uint64_t read_total(const uint64_t* at, hipStream_t s, const char* tag) {
-    uint64_t x = 0;
-    check_memcpy(hipMemcpyAsync(&x, at, sizeof(uint64_t), hipMemcpyDeviceToHost, s), tag);
-    check_sync(s, tag);
-    return x;
-}
+const Fail fail{"LiftIntervals"};
+static_assert(LIFT_MAX_CHAINS == POST_MAX_CHAINS && LIFT_MAX_BLOCKS == POST_MAX_BLOCKS && LIFT_TOP == POST_TOP,
+              "checked_block_pairs holds the chains to the limits lift.hip's kernels are written for");
 
 }  // namespace
 
@@ -82,7 +38,7 @@ size_t sa_lift_intervals(const uint32_t* first, const uint32_t* block_start, con
     if (P.den < 1 || P.den > LIFT_MAX_DEN) fail("den = %lld: 1 .. 1 << 20", P.den);
     if (P.num > P.den) fail("num = %lld exceeds den = %lld", P.num, P.den);
     if (n_intervals > LIFT_MAX_INTERVALS) fail("%lld intervals: at most 1 << 26", (long long)n_intervals);
-    const uint32_t B = checked_blocks(first, block_start, block_end, oblock_start, oblock_end, ostrand, n_chains);
+    const uint32_t B = checked_block_pairs(fail, first, block_start, block_end, oblock_start, oblock_end, ostrand, n_chains);
     for (size_t k = 0; k < n_intervals; k++) {
         if (iv_start[k] >= iv_end[k]) fail("interval %lld: start >= end", (long long)k);
         if (iv_end[k] >= LIFT_TOP) fail("interval %lld ends at or past 2^31", (long long)k);
@@ -127,10 +83,6 @@ size_t sa_lift_intervals(const uint32_t* first, const uint32_t* block_start, con
     a.be = d_be;
     a.obs = d_obs;
     a.obe = d_obe;
-    a.group = group ? d_group : nullptr;
-    a.ogroup = ogroup ? d_ogroup : nullptr;
-    a.ostrand = ostrand ? d_ostrand : nullptr;
-    a.iv_group = iv_group ? d_ivg : nullptr;
     a.iv_s = d_ivs;
     a.iv_e = d_ive;
 
@@ -139,10 +91,10 @@ size_t sa_lift_intervals(const uint32_t* first, const uint32_t* block_start, con
     to_device(d_be, block_end, B, s, "lift: block ends");
     to_device(d_obs, oblock_start, B, s, "lift: other block starts");
     to_device(d_obe, oblock_end, B, s, "lift: other block ends");
-    if (group) to_device(d_group, group, N, s, "lift: group");
-    if (ogroup) to_device(d_ogroup, ogroup, N, s, "lift: ogroup");
-    if (ostrand) to_device(d_ostrand, ostrand, N, s, "lift: ostrand");
-    if (iv_group) to_device(d_ivg, iv_group, I, s, "lift: interval groups");
+    a.group = upload(d_group, group, N, s, "lift: group");
+    a.ogroup = upload(d_ogroup, ogroup, N, s, "lift: ogroup");
+    a.ostrand = upload(d_ostrand, ostrand, N, s, "lift: ostrand");
+    a.iv_group = upload(d_ivg, iv_group, I, s, "lift: interval groups");
     to_device(d_ivs, iv_start, I, s, "lift: interval starts");
     to_device(d_ive, iv_end, I, s, "lift: interval ends");
 
@@ -162,7 +114,7 @@ size_t sa_lift_intervals(const uint32_t* first, const uint32_t* block_start, con
         launch_lift_count(a, s);
         launch_exclusive_scan_u64(a.cnt, a.off, I, temp, s);
     });
-    const uint64_t H64 = read_total(a.off + I, s, "lift_count");
+    const uint64_t H64 = read_u64(a.off + I, s, "lift_count");
     if (H64 > LIFT_MAX_OUT) fail("%lld hits: at most 2^31 - 1", (long long)H64);
     const uint32_t H = (uint32_t)H64;
     a.H = H;
@@ -174,7 +126,7 @@ size_t sa_lift_intervals(const uint32_t* first, const uint32_t* block_start, con
     uint32_t O = 0;
     if (a.with_blocks && H) {
         launch(sl, "lift_blocks", [&] { launch_exclusive_scan_u64(a.hn, a.hoff, H, htemp, s); });
-        const uint64_t O64 = read_total(a.hoff + H, s, "lift_blocks");
+        const uint64_t O64 = read_u64(a.hoff + H, s, "lift_blocks");
         if (O64 > LIFT_MAX_OUT) fail("%lld output blocks: at most 2^31 - 1", (long long)O64);
         a.O = O = (uint32_t)O64;
         sl->lift_out.ensure((size_t)O * sizeof(sa_lift_block), "lift blocks");
@@ -186,10 +138,10 @@ size_t sa_lift_intervals(const uint32_t* first, const uint32_t* block_start, con
     sa_lift_hit* hit = host_alloc<sa_lift_hit>(H, WHO);
     sa_lift_block* blk = host_alloc<sa_lift_block>(O, WHO);
     std::vector<LiftRange> range(I);
-    check_memcpy(hipMemcpyAsync(rec, a.rec, (size_t)I * sizeof(sa_lift_record), hipMemcpyDeviceToHost, s), "lift: records");
-    check_memcpy(hipMemcpyAsync(range.data(), a.range, (size_t)I * sizeof(LiftRange), hipMemcpyDeviceToHost, s), "lift: ranges");
-    if (H) check_memcpy(hipMemcpyAsync(hit, a.hits, (size_t)H * sizeof(sa_lift_hit), hipMemcpyDeviceToHost, s), "lift: hits");
-    if (O) check_memcpy(hipMemcpyAsync(blk, a.out, (size_t)O * sizeof(sa_lift_block), hipMemcpyDeviceToHost, s), "lift: blocks");
+    to_host(rec, a.rec, I, s, "lift: records");
+    to_host(range.data(), a.range, I, s, "lift: ranges");
+    to_host(hit, a.hits, H, s, "lift: hits");
+    to_host(blk, a.out, O, s, "lift: blocks");
     check_sync(s, "lift_emit");
     st.prep_ms = (float)ev.ms(0, 1);
     st.lift_ms = (float)ev.ms(1, 2);

@@ -74,19 +74,16 @@ size_t sa_net_chains(const uint32_t* first, const uint32_t* block_start, const u
         c.take(temp, temp_bytes);
     });
     a.first = d_first; a.bs = d_bs; a.be = d_be; a.score = d_score;
-    a.group = group ? d_group : nullptr;
     a.n = N;
     a.blocks = B;
     a.min_space = P.min_space;
     a.min_fill = P.min_fill;
 
-    check_memcpy(hipMemcpyAsync(d_first, first, ((size_t)N + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s), "net: first");
-    if (B) {
-        check_memcpy(hipMemcpyAsync(d_bs, block_start, (size_t)B * sizeof(uint32_t), hipMemcpyHostToDevice, s), "net: block starts");
-        check_memcpy(hipMemcpyAsync(d_be, block_end, (size_t)B * sizeof(uint32_t), hipMemcpyHostToDevice, s), "net: block ends");
-    }
-    check_memcpy(hipMemcpyAsync(d_score, score, (size_t)N * sizeof(int64_t), hipMemcpyHostToDevice, s), "net: scores");
-    if (group) check_memcpy(hipMemcpyAsync(d_group, group, (size_t)N * sizeof(uint32_t), hipMemcpyHostToDevice, s), "net: groups");
+    to_device(d_first, first, (size_t)N + 1, s, "net: first");
+    to_device(d_bs, block_start, B, s, "net: block starts");
+    to_device(d_be, block_end, B, s, "net: block ends");
+    to_device(d_score, score, N, s, "net: scores");
+    a.group = upload(d_group, group, N, s, "net: groups");
 
     // prepare: stable sort by score descending from input order, then by group; hulls and group ranges; the blocks' prefix sums
     ev.mark(0);
@@ -103,7 +100,7 @@ size_t sa_net_chains(const uint32_t* first, const uint32_t* block_start, const u
     });
     ev.mark(1);
     uint64_t groups64 = 0;
-    check_memcpy(hipMemcpyAsync(&groups64, a.gidx + N, sizeof(uint64_t), hipMemcpyDeviceToHost, s), "net: groups");
+    to_host(&groups64, a.gidx + N, 1, s, "net: groups");
     check_sync(s, "net_prepare");
     const uint32_t G = (uint32_t)groups64;
     if (G == 0 || G > N) {
@@ -134,8 +131,8 @@ size_t sa_net_chains(const uint32_t* first, const uint32_t* block_start, const u
             launch_exclusive_scan_u64(r.cnt, r.off, 2 * (uint64_t)S, scan_temp, s);
         });
         uint64_t children = 0, end = 0;
-        check_memcpy(hipMemcpyAsync(&children, r.off + S, sizeof(uint64_t), hipMemcpyDeviceToHost, s), "net: children");
-        check_memcpy(hipMemcpyAsync(&end, r.off + 2 * (size_t)S, sizeof(uint64_t), hipMemcpyDeviceToHost, s), "net: fills");
+        to_host(&children, r.off + S, 1, s, "net: children");
+        to_host(&end, r.off + 2 * (size_t)S, 1, s, "net: fills");
         check_sync(s, "net round");
         st.rounds++;
         st.spaces += S;
@@ -182,7 +179,7 @@ size_t sa_net_chains(const uint32_t* first, const uint32_t* block_start, const u
             launch_net_finish(d_fills, order, inv, F, sorted, s);
         });
         ev.mark(3);
-        check_memcpy(hipMemcpyAsync(out, sorted, (size_t)F * sizeof(sa_net_fill), hipMemcpyDeviceToHost, s), "net: fills");
+        to_host(out, sorted, F, s, "net: fills");
     } else {
         ev.mark(3);
     }

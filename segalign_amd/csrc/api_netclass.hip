@@ -11,49 +11,16 @@ namespace {
 
 const char* const WHO = "NetClassify";
 
-void fail(const char* fmt, long long a = 0, long long b = 0) {
-    fprintf(stderr, "Error: NetClassify: ");
-    fprintf(stderr, fmt, a, b);
-    fprintf(stderr, "\n");
-    exit(1);
-}
-
-// The CSR and block rules of sa_net_chains and the rules of the other axis, in one pass.  Returns the number of blocks.
-uint32_t checked_blocks(const uint32_t* first, const uint32_t* bs, const uint32_t* be, const uint32_t* obs, const uint32_t* obe,
-                        const uint8_t* ostrand, size_t n) {
-    if (n > NETCLASS_MAX_CHAINS) fail("%lld chains: at most 1 << 22", (long long)n);
-    if (n == 0) return 0;
-    if (first[0] != 0) fail("first[0] = %lld, not 0", first[0]);
-    for (size_t c = 0; c < n; c++) {
-        if (first[c + 1] < first[c]) fail("first[] decreases at chain %lld", (long long)c);
-        if (first[c + 1] > NETCLASS_MAX_BLOCKS) fail("%lld blocks: at most 1 << 26", first[c + 1]);
-        const uint32_t strand = ostrand ? ostrand[c] : 0;
-        if (strand > 1) fail("ostrand[%lld] = %lld: 0 or 1", (long long)c, strand);
-        for (size_t k = first[c]; k < first[c + 1]; k++) {
-            if (bs[k] >= be[k]) fail("chain %lld, block %lld: start >= end", (long long)c, (long long)k);
-            if (be[k] >= NETCLASS_TOP) fail("chain %lld, block %lld ends at or past 2^31", (long long)c, (long long)k);
-            if (k > first[c] && be[k - 1] > bs[k]) fail("chain %lld: its blocks overlap or descend at block %lld", (long long)c, (long long)k);
-            if (obs[k] >= obe[k]) fail("chain %lld, block %lld: start >= end on the other axis", (long long)c, (long long)k);
-            if (obe[k] >= NETCLASS_TOP) fail("chain %lld, block %lld ends at or past 2^31 on the other axis", (long long)c, (long long)k);
-            if (obe[k] - obs[k] != be[k] - bs[k]) fail("chain %lld, block %lld: the lengths on the two axes differ", (long long)c, (long long)k);
-            if (k > first[c] && (strand ? obe[k] > obs[k - 1] : obe[k - 1] > obs[k]))
-                fail(strand ? "chain %lld (ostrand 1): its other blocks overlap or ascend at block %lld"
-                            : "chain %lld (ostrand 0): its other blocks overlap or descend at block %lld",
-                     (long long)c, (long long)k);
-        }
-    }
-    return first[n];
-}
+const Fail fail{"NetClassify"};
+static_assert(NETCLASS_MAX_CHAINS == POST_MAX_CHAINS && NETCLASS_MAX_BLOCKS == POST_MAX_BLOCKS && NETCLASS_TOP == POST_TOP,
+              "checked_block_pairs holds the chains to the limits netclass.hip's kernels are written for");
 
 // The rules of the fills; returns the number of clipped blocks.
 uint64_t checked_fills(const sa_net_fill* fills, size_t F, const uint32_t* first, const uint32_t* bs, const uint32_t* be, size_t n_chains) {
     uint64_t blocks = 0;
     for (size_t k = 0; k < F; k++) {
         const sa_net_fill& f = fills[k];
-        if (f.start >= f.end) fail("fill %lld: start >= end", (long long)k);
-        if (f.chain >= n_chains) fail("fill %lld names chain %lld, which is not in the input", (long long)k, f.chain);
-        if (f.n_blocks < 1 || f.first_block < first[f.chain] || (uint64_t)f.first_block + f.n_blocks > first[f.chain + 1])
-            fail("fill %lld: its blocks leave chain %lld", (long long)k, f.chain);
+        checked_fill_in_chain(fail, f, k, first, n_chains);
         if (be[f.first_block] <= f.start || bs[f.first_block + f.n_blocks - 1] >= f.end)
             fail("fill %lld: its first block ends before its start or its last block starts after its end", (long long)k);
         blocks += f.n_blocks;
@@ -89,7 +56,7 @@ size_t sa_net_classify(const uint32_t* first, const uint32_t* block_start, const
     if (P.min_ali > NETCLASS_TOP) fail("min_ali = %lld out of range", P.min_ali);
     if (P.max_far > NETCLASS_TOP) fail("max_far = %lld out of range", P.max_far);
     if (n_fills > NETCLASS_MAX_FILLS) fail("%lld fills: at most 2^31 - 1", (long long)n_fills);
-    const uint32_t B = checked_blocks(first, block_start, block_end, oblock_start, oblock_end, ostrand, n_chains);
+    const uint32_t B = checked_block_pairs(fail, first, block_start, block_end, oblock_start, oblock_end, ostrand, n_chains);
     const uint64_t blocks = checked_fills(fills, n_fills, first, block_start, block_end, n_chains);
     if (n_fills == 0) return 0;
     const uint32_t N = (uint32_t)n_chains, F = (uint32_t)n_fills, M = (uint32_t)blocks, E = 2 * M;
@@ -123,16 +90,14 @@ size_t sa_net_classify(const uint32_t* first, const uint32_t* block_start, const
     a.be = d_be;
     a.obs = d_obs;
     a.obe = d_obe;
-    a.ogroup = ogroup ? d_ogroup : nullptr;
-    a.ostrand = ostrand ? d_ostrand : nullptr;
 
-    check_memcpy(hipMemcpyAsync(d_fills, fills, (size_t)F * sizeof(sa_net_fill), hipMemcpyHostToDevice, s), "net class: fills");
-    check_memcpy(hipMemcpyAsync(d_bs, block_start, (size_t)B * sizeof(uint32_t), hipMemcpyHostToDevice, s), "net class: block starts");
-    check_memcpy(hipMemcpyAsync(d_be, block_end, (size_t)B * sizeof(uint32_t), hipMemcpyHostToDevice, s), "net class: block ends");
-    check_memcpy(hipMemcpyAsync(d_obs, oblock_start, (size_t)B * sizeof(uint32_t), hipMemcpyHostToDevice, s), "net class: other block starts");
-    check_memcpy(hipMemcpyAsync(d_obe, oblock_end, (size_t)B * sizeof(uint32_t), hipMemcpyHostToDevice, s), "net class: other block ends");
-    if (ogroup) check_memcpy(hipMemcpyAsync(d_ogroup, ogroup, (size_t)N * sizeof(uint32_t), hipMemcpyHostToDevice, s), "net class: ogroup");
-    if (ostrand) check_memcpy(hipMemcpyAsync(d_ostrand, ostrand, (size_t)N, hipMemcpyHostToDevice, s), "net class: ostrand");
+    to_device(d_fills, fills, F, s, "net class: fills");
+    to_device(d_bs, block_start, B, s, "net class: block starts");
+    to_device(d_be, block_end, B, s, "net class: block ends");
+    to_device(d_obs, oblock_start, B, s, "net class: other block starts");
+    to_device(d_obe, oblock_end, B, s, "net class: other block ends");
+    a.ogroup = upload(d_ogroup, ogroup, N, s, "net class: ogroup");
+    a.ostrand = upload(d_ostrand, ostrand, N, s, "net class: ostrand");
 
     Timer<2> ev(s, "net class timing");
     ev.mark(0);
@@ -156,7 +121,7 @@ size_t sa_net_classify(const uint32_t* first, const uint32_t* block_start, const
     });
     ev.mark(1);
     sa_net_class* out = host_alloc<sa_net_class>(F, WHO);
-    check_memcpy(hipMemcpyAsync(out, a.out, (size_t)F * sizeof(sa_net_class), hipMemcpyDeviceToHost, s), "net class: records");
+    to_host(out, a.out, F, s, "net class: records");
     check_sync(s, "netclass_classes");
     st.class_ms = (float)ev.ms(0, 1);
     prof_flush(sl);

@@ -11,12 +11,8 @@ namespace {
 
 const char* const WHO = "NetSubset";
 
-void fail(const char* fmt, long long a = 0, long long b = 0) {
-    fprintf(stderr, "Error: NetSubset: ");
-    fprintf(stderr, fmt, a, b);
-    fprintf(stderr, "\n");
-    exit(1);
-}
+const Fail fail{"NetSubset"};
+static_assert(NETSUBSET_MAX_MEMBERS == POST_MAX_MEMBERS, "checked_first holds the members to the limit netsubset.hip's kernels are written for");
 
 struct Span {  // a member's block on the axis
     uint64_t s, e;
@@ -30,21 +26,9 @@ Span span_of(const sa_segment_pair& h, int axis) {
 // The CSR rules of sa_stitch_chains; returns the HSP of every member entry, in member order.
 std::vector<sa_segment_pair> checked_members(const sa_segment_pair* hsps, size_t n_hsps, const uint32_t* members, const uint32_t* first,
                                              size_t n_chains, const NetSubsetArgs& a) {
-    if (n_chains > NETSUBSET_MAX_MEMBERS) fail("%lld chains: at most 1 << 22", (long long)n_chains);
-    if (n_chains == 0) return {};
-    if (first[0] != 0) fail("first[0] = %lld, not 0", first[0]);
-    for (size_t c = 0; c < n_chains; c++)
-        if (first[c + 1] < first[c]) fail("first[] decreases at chain %lld", (long long)c);
-    const size_t M = first[n_chains];
-    if (M > NETSUBSET_MAX_MEMBERS) fail("%lld members: at most 1 << 22", (long long)M);
+    const size_t M = checked_first(fail, first, n_chains);
     std::vector<sa_segment_pair> mh(M);
-    for (size_t k = 0; k < M; k++) {
-        if (members[k] >= n_hsps) fail("member %lld names HSP %lld, which is not in the input", (long long)k, members[k]);
-        const sa_segment_pair& h = hsps[members[k]];
-        if ((uint64_t)h.ref_start + h.len + 1 > a.ref_len || (uint64_t)h.query_start + h.len + 1 > a.query_len)
-            fail("member %lld (HSP %lld) does not lie inside the block", (long long)k, members[k]);
-        mh[k] = h;
-    }
+    for (size_t k = 0; k < M; k++) mh[k] = checked_member(fail, hsps, n_hsps, members, k, a.ref_len, a.query_len);
     for (size_t c = 0; c < n_chains; c++)
         for (size_t k = first[c]; k + 1 < first[c + 1]; k++) {
             const sa_segment_pair &x = mh[k], &y = mh[k + 1];
@@ -63,10 +47,7 @@ Counts checked_fills(const sa_net_fill* fills, size_t F, const std::vector<sa_se
     Counts n;
     for (size_t k = 0; k < F; k++) {
         const sa_net_fill& f = fills[k];
-        if (f.start >= f.end) fail("fill %lld: start >= end", (long long)k);
-        if (f.chain >= n_chains) fail("fill %lld names chain %lld, which is not in the input", (long long)k, f.chain);
-        if (f.n_blocks < 1 || f.first_block < first[f.chain] || (uint64_t)f.first_block + f.n_blocks > first[f.chain + 1])
-            fail("fill %lld: its blocks leave chain %lld", (long long)k, f.chain);
+        checked_fill_in_chain(fail, f, k, first, n_chains);
         const Span b0 = span_of(mh[f.first_block], axis), b1 = span_of(mh[f.first_block + f.n_blocks - 1], axis);
         if (b0.e <= f.start || b1.s >= f.end) fail("fill %lld: its first block ends before its start or its last block starts after its end", (long long)k);
         n.out += f.n_blocks;
@@ -168,8 +149,8 @@ size_t sa_net_subset(const sa_segment_pair* hsps, size_t n_hsps, const uint32_t*
     a.image = costs.on ? d_image : nullptr;
 
     Timer<4> ev(s, "net subset timing");  // 0-1 up to the counts, 2-3 the rest
-    check_memcpy(hipMemcpyAsync(d_fills, fills, (size_t)F * sizeof(sa_net_fill), hipMemcpyHostToDevice, s), "net subset: fills");
-    check_memcpy(hipMemcpyAsync(d_mh, mh.data(), (size_t)M * sizeof(sa_segment_pair), hipMemcpyHostToDevice, s), "net subset: members");
+    to_device(d_fills, fills, F, s, "net subset: fills");
+    to_device(d_mh, mh.data(), M, s, "net subset: members");
     if (costs.on) check_memcpy(hipMemcpyAsync(d_image, costs.w, sizeof(costs.w), hipMemcpyHostToDevice, s), "net subset: gap costs");
     ev.mark(0);
     launch(sl, "netsubset_offsets", [&] {
@@ -186,8 +167,8 @@ size_t sa_net_subset(const sa_segment_pair* hsps, size_t n_hsps, const uint32_t*
     });
     ev.mark(1);
     uint64_t runs64 = 0, cut64 = 0;
-    check_memcpy(hipMemcpyAsync(&runs64, a.run + N, sizeof(uint64_t), hipMemcpyDeviceToHost, s), "net subset: runs");
-    check_memcpy(hipMemcpyAsync(&cut64, a.cut_at + N, sizeof(uint64_t), hipMemcpyDeviceToHost, s), "net subset: cut members");
+    to_host(&runs64, a.run + N, 1, s, "net subset: runs");
+    to_host(&cut64, a.cut_at + N, 1, s, "net subset: cut members");
     check_sync(s, "netsubset_emit");
     if (runs64 < F || runs64 > N || cut64 != n.cut) {
         fprintf(stderr, "Error: NetSubset: %llu runs and %llu cut members from %u fills, %u members and %llu cut members\n",
@@ -206,8 +187,8 @@ size_t sa_net_subset(const sa_segment_pair* hsps, size_t n_hsps, const uint32_t*
     ev.mark(3);
     sa_segment_pair* out = host_alloc<sa_segment_pair>(N, WHO);
     sa_subset_chain* rec = host_alloc<sa_subset_chain>(R, WHO);
-    check_memcpy(hipMemcpyAsync(out, a.out, (size_t)N * sizeof(sa_segment_pair), hipMemcpyDeviceToHost, s), "net subset: output HSPs");
-    check_memcpy(hipMemcpyAsync(rec, a.chains, (size_t)R * sizeof(sa_subset_chain), hipMemcpyDeviceToHost, s), "net subset: sub-chains");
+    to_host(out, a.out, N, s, "net subset: output HSPs");
+    to_host(rec, a.chains, R, s, "net subset: sub-chains");
     check_sync(s, "netsubset_chains");
     st.subset_ms = ev.ms(0, 1) + ev.ms(2, 3);
     prof_flush(sl);

@@ -11,12 +11,7 @@ using namespace sa;
 
 namespace {
 
-void fail(const char* fmt, long long a = 0, long long b = 0) {
-    fprintf(stderr, "Error: StitchChains: ");
-    fprintf(stderr, fmt, a, b);
-    fprintf(stderr, "\n");
-    exit(1);
-}
+const Fail fail{"StitchChains"};
 
 struct Params {
     int gap_open, gap_extend, max_link, min_link_score;
@@ -62,26 +57,11 @@ struct Chains {
     std::vector<uint32_t> runs;
 };
 
-// The checks of the chain list; returns the number of member entries, 0 for nothing to do.
-size_t checked_first(const uint32_t* first, size_t n_chains) {
-    if (n_chains > (1u << 22)) fail("%lld chains: at most 1 << 22", (long long)n_chains);
-    if (n_chains == 0) return 0;
-    if (first[0] != 0) fail("first[0] = %lld, not 0", first[0]);
-    for (size_t c = 0; c < n_chains; c++)
-        if (first[c + 1] < first[c]) fail("first[] decreases at chain %lld", (long long)c);
-    const size_t M = first[n_chains];
-    if (M > (1u << 22)) fail("%lld members: at most 1 << 22", (long long)M);
-    return M;
-}
-
 // The M member entries, each checked to name an HSP of the input that lies inside the block.
 std::vector<StitchMember> checked_members(const sa_segment_pair* hsps, size_t n_hsps, const uint32_t* members, size_t M, const StitchArgs& a) {
     std::vector<StitchMember> mem(M);
     for (size_t k = 0; k < M; k++) {
-        if (members[k] >= n_hsps) fail("member %lld names HSP %lld, which is not in the input", (long long)k, members[k]);
-        const sa_segment_pair& h = hsps[members[k]];
-        if ((uint64_t)h.ref_start + h.len + 1 > a.ref_len || (uint64_t)h.query_start + h.len + 1 > a.query_len)
-            fail("member %lld (HSP %lld) does not lie inside the block", (long long)k, members[k]);
+        const sa_segment_pair& h = checked_member(fail, hsps, n_hsps, members, k, a.ref_len, a.query_len);
         mem[k] = {h.ref_start, h.query_start, h.len, 0};
     }
     return mem;
@@ -117,11 +97,11 @@ void member_scores(Slot* sl, const StitchArgs& a, Chains& C, sa_stitch_stats& st
     StitchMemberOut* d_mo;
     carve(sl->stitch, "stitch", [&](Carve& c) { c.take(d_mem, M).take(d_mo, M); });
     Timer<2> tm(s, "stitch timing");
-    check_memcpy(hipMemcpyAsync(d_mem, C.mem.data(), M * sizeof(StitchMember), hipMemcpyHostToDevice, s), "stitch members");
+    to_device(d_mem, C.mem.data(), M, s, "stitch members");
     tm.mark(0);
     launch(sl, "stitch_members", [&] { launch_stitch_members(a, d_mem, (uint32_t)M, d_mo, s); });
     tm.mark(1);
-    check_memcpy(hipMemcpyAsync(C.mo.data(), d_mo, M * sizeof(StitchMemberOut), hipMemcpyDeviceToHost, s), "stitch member scores");
+    to_host(C.mo.data(), d_mo, M, s, "stitch member scores");
     check_sync(s, "stitch_members");
     st.member_ms = tm.ms(0, 1);
 }
@@ -163,14 +143,14 @@ void walk_batch(Slot* sl, const GappedArgs& ga, const BatchBufs& d, size_t nops,
                 Chains& C, Timer<3>& tm, sa_stitch_stats& st) {
     const hipStream_t s = sl->stream;
     const size_t w = wt.size();
-    check_memcpy(hipMemcpyAsync(d.walk, wt.data(), w * sizeof(TraceTask), hipMemcpyHostToDevice, s), "stitch walk tasks");
+    to_device(d.walk, wt.data(), w, s, "stitch walk tasks");
     tm.mark(1);
     launch(sl, "stitch_walk", [&] { launch_gapped_walk(ga, d.walk, (uint32_t)w, d.area, d.ops, d.out, s); });
     tm.mark(2);
     std::vector<TraceOut> wo(w);
     std::vector<uint32_t> bops(nops);
-    check_memcpy(hipMemcpyAsync(wo.data(), d.out, w * sizeof(TraceOut), hipMemcpyDeviceToHost, s), "stitch walk results");
-    check_memcpy(hipMemcpyAsync(bops.data(), d.ops, nops * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "stitch ops");
+    to_host(wo.data(), d.out, w, s, "stitch walk results");
+    to_host(bops.data(), d.ops, nops, s, "stitch ops");
     check_sync(s, "stitch_walk");
     st.walk_ms += tm.ms(1, 2);
     for (size_t k = 0; k < w; k++) {
@@ -195,12 +175,12 @@ void sweep_batch(Slot* sl, const StitchArgs& a, const GappedArgs& ga, const Para
     carve(sl->stitch, "stitch", [&](Carve& c) {
         c.take(d.tasks, m).take(d.walk, m).take(d.out, m).take(d.score, m).take(d.ops, bt.nops).take(d.area, bt.trace);
     });
-    check_memcpy(hipMemcpyAsync(d.tasks, bt.tasks.data(), m * sizeof(TraceTask), hipMemcpyHostToDevice, s), "stitch tasks");
+    to_device(d.tasks, bt.tasks.data(), m, s, "stitch tasks");
     tm.mark(0);
     launch(sl, "stitch_sweep", [&] { launch_stitch_sweep(a, ga.max_band, d.tasks, (uint32_t)m, d.area, d.score, s); });
     tm.mark(1);
     std::vector<int32_t> sc(m);
-    check_memcpy(hipMemcpyAsync(sc.data(), d.score, m * sizeof(int32_t), hipMemcpyDeviceToHost, s), "stitch scores");
+    to_host(sc.data(), d.score, m, s, "stitch scores");
     check_sync(s, "stitch_sweep");
     st.sweep_ms += tm.ms(0, 1);
     st.trace_bytes += bt.trace;
@@ -324,7 +304,7 @@ size_t sa_stitch_chains(const sa_segment_pair* hsps, size_t n_hsps, const uint32
     if (stats) *stats = st;
     require_proc(who, buffer);
     const Params P = resolve(p);
-    const size_t M = checked_first(first, n_chains);
+    const size_t M = checked_first(fail, first, n_chains);
     if (M == 0) return 0;
 
     Slot* sl = acquire_slot();

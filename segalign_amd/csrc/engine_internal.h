@@ -19,7 +19,9 @@
 //   api_netclass.hip   sa_net_classify: the fills of a net classed against their parents on the other axis, with duplication and the filter (netclass.hip)
 //   api_lift.hip       sa_lift_intervals: intervals of one axis carried through chains to the other axis (lift.hip)
 //   api_fill.hip       sa_fill_chains: the links of chains filled with HSPs from a sweep of every diagonal (fill.hip)
-//   post_host.h        what those seven share on the host: event timing, checked launches, buffer carving, caller-owned arrays, trace batches
+//   post_host.h        what those entries and api_chaintrim.hip share on the host: event timing, checked launches and copies, buffer carving,
+//                      caller-owned arrays, trace batches
+//   post_checks.h      the input rules they share, free of HIP: chain lists, their members, block pairs, the head of the fill rules
 //   gapped.hip         kernels of the gapped entries: y-drop extension of a side, trace sweep, path walk (gapped.h)
 //   cover.hip          kernels and rocPRIM steps of the greedy cover index; its sort and scan wrappers also serve api_hspchain.hip (gapped.h)
 //   hspchain.hip       kernels of the chaining DP: rank keys, gather, tile cross / resolve with or without a gap-cost table, group ends,

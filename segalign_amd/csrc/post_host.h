@@ -1,11 +1,13 @@
-// post_host.h -- the host helpers that the post-processing entries share (api_gapped.hip, api_hspchain.hip, api_stitch.hip, api_net.hip,
-// api_netsubset.hip, api_netclass.hip, api_lift.hip, api_fill.hip): device time between events, profiled and checked launches, carving a slot buffer, malloc-ed arrays for
-// the caller, the resident block as kernel arguments, the checked gap-cost table as its device image, and the trace batches' packing and
-// runs.  Host code only, everything inline or a template.
+// post_host.h -- the host helpers that the nine post-processing units share (api_gapped.hip, api_hspchain.hip, api_stitch.hip,
+// api_chaintrim.hip, api_fill.hip, api_net.hip, api_netsubset.hip, api_netclass.hip, api_lift.hip): device time between
+// events, profiled and checked launches, carving a slot buffer, the checked copies to and from the device, malloc-ed arrays for the
+// caller, the resident block as kernel arguments, the checked gap-cost table as its device image, and the trace batches' packing and
+// runs; and through post_checks.h the input rules they share.  Host code only, everything inline or a template.
 #pragma once
 #include "engine_internal.h"
 #include "gapped.h"
 #include "hspcost.h"
+#include "post_checks.h"
 
 namespace sa {
 
@@ -83,6 +85,30 @@ T* malloc_copy(const std::vector<T>& v, const char* who) {
     T* p = host_alloc<T>(v.size(), who);
     if (p) memcpy(p, v.data(), v.size() * sizeof(T));
     return p;
+}
+
+// Checked copies on a stream, typed and counted in elements; nothing is enqueued for n == 0.  tag: the copy's name in the exit-13 message.
+template <typename T>
+void to_device(T* dst, const T* src, size_t n, hipStream_t s, const char* tag) {
+    if (n) check_memcpy(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, s), tag);
+}
+template <typename T>
+void to_host(T* dst, const T* src, size_t n, hipStream_t s, const char* tag) {
+    if (n) check_memcpy(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, s), tag);
+}
+// An optional input array as the kernels take it: nullptr for none, else its n elements copied to dst, and dst.
+template <typename T>
+T* upload(T* dst, const T* src, size_t n, hipStream_t s, const char* tag) {
+    if (!src) return nullptr;
+    to_device(dst, src, n, s, tag);
+    return dst;
+}
+// One total read back, with the synchronise that makes it valid.  Two totals of one step take two to_host and one check_sync instead.
+inline uint64_t read_u64(const uint64_t* at, hipStream_t s, const char* tag) {
+    uint64_t x = 0;
+    to_host(&x, at, 1, s, tag);
+    check_sync(s, tag);
+    return x;
 }
 
 // The resident target block and the query strand (rev, buffer) of the slot's device into the fields that GappedArgs and StitchArgs
