@@ -915,6 +915,11 @@ constexpr int CLS_TAB = 4096;                       // 12-bit fields: six bases
 constexpr int CLS_TAIL = 256;                       // the left context ends with a four-base field (64 = 10 x 6 + 4)
 constexpr int CLS_LDS_DWORDS = CLS_TAB + CLS_TAIL;  // 4-byte entries: 16 KB + 1 KB
 constexpr bool CLS_TRACK_DROP = true;               // keep the lowest N seen at a field end (see cls_step)
+// per-wave tiles of the one-copy form (see the kernel): 64 position records and 64 dwords of either strand's unshifted 2-bit copy
+constexpr int CLS_TILE = 64;
+constexpr int CLS_WIN_DWORDS = 5;                                 // dwords a window takes from the unshifted copy
+constexpr uint32_t CLS_WIN_SPAN = CLS_TILE - CLS_WIN_DWORDS;      // a window may start at tile dwords 0 .. 59
+constexpr int CLS_TILE_BYTES = CLS_TILE * (int)sizeof(TdRec) + 2 * CLS_TILE * 4;  // 1.5 KB per wave
 
 // entry of a field: {sum : sum - mx} as two int16 (sum = score of the field, mx = its largest prefix score, >= 0)
 __device__ __forceinline__ void cls_table_init(uint32_t* __restrict__ s_cls, const int* cls, int nthreads) {
@@ -982,17 +987,23 @@ __device__ __forceinline__ uint32_t cls_seed_state(const ExtendArgs& a) {
 // whose windows lie in 13 different copies x 2 strands = 26 lines per buffer that miss the L1 every time and the L2 half of the time
 // (the record stream flushes both): 3.1 HBM lines per 160-byte run where a bare walk of the same runs needs 2.1
 // (tools/micro/hit_shaped.hip).  From copy 0 the windows of consecutive positions share their lines.
+// Per-wave tiles (profiles/cls_tiles): a buffer's request used to issue seven vector loads -- two for the record, five
+// for per-position data: the TdRec gather and the two five-dword windows -- although a wave's 64 buffers hold about 63 consecutive
+// positions, so it asked the L1 for the same few lines 64 times.  They were L1 or L2 hits nearly every time (HBM lines per launch did
+// not move when they went), but every one of them passed through the L1's request path, which is what bounds the kernel.  Now the
+// wave keeps 64 position records and 64 dwords of either strand's copy 0 in LDS (1.5 KB per wave) and a request issues the two record
+// loads alone: vector loads per buffer 7.1 -> 2.1, L1 -> L2 requests -3.5 %, seven more LDS reads per buffer that add no bank
+// conflict (the lanes of a position read one address), +6.7 % on the default pass with six calls in flight.
 template <bool ONE_COPY>
 __global__ __launch_bounds__(CTX_THREADS_MAX, 8) void extend_filter_cls_kernel(ExtendArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t s_cls[CLS_LDS_DWORDS];  // 4-byte entry per 6-base class field (16 KB) + the 4-base tail fields (1 KB)
-    extern __shared__ L2Rec s_l2_dyn[];          // [waves of the workgroup][CTX_STAGE_CAP]
+    extern __shared__ __attribute__((aligned(16))) L2Rec s_l2_dyn[];  // [waves of the workgroup][CTX_STAGE_CAP], then (ONE_COPY) [waves][CLS_TILE_BYTES]
     cls_table_init(s_cls, a.cls, (int)blockDim.x);
     __syncthreads();
     const uint32_t* __restrict__ s_tail = s_cls + CLS_TAB;
     L2Rec* stage = s_l2_dyn + (threadIdx.x >> 6) * CTX_STAGE_CAP;
     int n_stage = 0;
     const int lane = threadIdx.x & 63;
-    const unsigned long long lane_lt = (1ull << lane) - 1ull;
     const int xdrop = a.xdrop;
     const uint4* __restrict__ ctx = reinterpret_cast<const uint4*>(a.td_ctx);
     const uint32_t seed_state = cls_seed_state(a);  // the left walk's {T : N} behind the seed window
@@ -1015,7 +1026,8 @@ __global__ __launch_bounds__(CTX_THREADS_MAX, 8) void extend_filter_cls_kernel(E
     // word, a running scalar count and two v_mbcnt -- no search, no shuffles (the TdCursor of 1b spends six ds_bpermute + ~40
     // VALU per buffer on the same question).  td_chunk gives the count at the wave's first hit.  The map is read through the
     // constant address space: a wave-uniform address there is a SCALAR load (s_load_dwordx2), no VALU or vector-memory slot.
-    // Latency: the head word is fetched four buffers ahead, the TdRec gather two and the records one buffer ahead (see the loop).
+    // Latency: the head word is fetched four buffers ahead, the TdRec gather two and the records one buffer ahead (see the loop); the
+    // one-copy form has no gather stage: its request reads the position records from the wave's tile in LDS.
     // Requests past the wave's range read valid memory (the next wave's buffers, the map's zero words, 16 KB of slack behind the
     // table) and are never used -- conditional loads would turn every s_waitcnt of the loop into a drain.
     typedef const uint64_t __attribute__((address_space(4))) * HeadPtr;
@@ -1042,14 +1054,75 @@ __global__ __launch_bounds__(CTX_THREADS_MAX, 8) void extend_filter_cls_kernel(E
         S.q[6] = __builtin_amdgcn_alignbit(ql3, ql2, 20);
     };
     uint64_t w0, w1, w2;  // head words of the buffers one, two and three ahead of the one being requested
-    TdRec hnext;          // TdRec of this lane's hit in the NEXT buffer to be requested
-    auto advance_map = [&](uint64_t b_req) {  // after the request of buffer b_req: gather for b_req + 1, map word for b_req + 4
-        hnext = a.td_rec[locate(w0)];
+    uint64_t wc = 0;      // (ONE_COPY) head word of the next buffer to be requested
+    TdRec hnext;          // TdRec of this lane's hit in the NEXT buffer to be requested (ONE_COPY: read from the tile by the request itself)
+    // ONE_COPY: the per-position data come out of three tiles in LDS that belong to the wave alone (no other wave reads or writes
+    // them, and the LDS serves a wave's instructions in order, so no barrier is involved):
+    //   s_td  td_rec[td0 .. td0 + 63]                          one 16-byte read per lane, the lanes of a position read one address
+    //   s_qr  dwords dr0 .. dr0 + 63 of this strand's copy 0   five dwords per lane from window dword (query_loc >> 4) - dr0 on
+    //   s_ql  the same of the other strand's copy from dl0 on; its positions DESCEND along a call, so a new tile ENDS at its first window
+    // A tile is loaded by ONE coalesced load of the wave (lanes past the end of the array stay on its last element) and lasts until a
+    // buffer has a lane outside it: then the wave loads it anew from that buffer's first lane on, in a wave-uniform branch.  The
+    // straight-line part of the loop holds the record loads alone.  A buffer whose windows spread over more than one tile (positions
+    // more than ~900 bases apart inside 64 hits: sparse calls) takes its windows from memory as the sixteen-copy form does.
+    // (the tiles are addressed as LDS explicitly: through generic pointers the compiler folds the tile reads and the fallback's reads
+    //  from memory into FLAT loads behind a pointer select, and every wait of the loop becomes a drain)
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef u32x4 __attribute__((address_space(3))) * LdsU4;
+    typedef uint32_t __attribute__((address_space(3))) * LdsU32;
+    LdsU4 s_td = nullptr;
+    LdsU32 s_qr = nullptr, s_ql = nullptr;
+    uint32_t td0 = 0, dr0 = 0, dl0 = 0;
+    const uint32_t q2_last = (uint32_t)(a.q2_stride >> 2) - 1u;  // last dword of a copy (q2_copy_stride: Q2_TAIL zero bytes behind the bases)
+    if (ONE_COPY) {
+        char* tiles = reinterpret_cast<char*>(s_l2_dyn) + (size_t)(blockDim.x >> 6) * (CTX_STAGE_CAP * sizeof(L2Rec)) + (size_t)(threadIdx.x >> 6) * CLS_TILE_BYTES;
+        s_td = (LdsU4)tiles;
+        s_qr = (LdsU32)(tiles + CLS_TILE * sizeof(TdRec));
+        s_ql = s_qr + CLS_TILE;
+    }
+    // (rare_lane: the lane number behind an empty asm, so that what the rare paths derive from it -- tile addresses, the audit's lane
+    //  mask -- is computed there and holds no register over the loop: eight waves per SIMD allow 64 VGPRs, and hoisted they spilled)
+    auto rare_lane = [&]() -> uint32_t {
+        uint32_t l = (uint32_t)lane;
+        asm volatile("" : "+v"(l));
+        return l;
+    };
+    auto tile_td = [&](uint32_t base) {  // (td_rec holds td_m + 1 records)
+        const uint32_t l = rare_lane();
+        const TdRec r = a.td_rec[min(base + l, a.td_m)];
+        __builtin_amdgcn_wave_barrier();
+        s_td[l] = u32x4{r.prefix, r.qpos, (uint32_t)r.off, (uint32_t)(r.off >> 32)};
+        __builtin_amdgcn_wave_barrier();
+        td0 = base;
+    };
+    auto tile_q = [&](uint32_t own_dword, uint32_t other_dword) {  // window dwords of the buffer's first lane
+        const uint32_t nr = own_dword, nl = other_dword > CLS_WIN_SPAN ? other_dword - CLS_WIN_SPAN : 0u;
+        const uint32_t l = rare_lane();
+        const uint32_t vr = reinterpret_cast<const uint32_t*>(a.q2_own)[min(nr + l, q2_last)];
+        const uint32_t vl = reinterpret_cast<const uint32_t*>(a.q2_other)[min(nl + l, q2_last)];
+        __builtin_amdgcn_wave_barrier();
+        s_qr[l] = vr;
+        s_ql[l] = vl;
+        __builtin_amdgcn_wave_barrier();
+        dr0 = nr;
+        dl0 = nl;
+    };
+    auto advance_map = [&](uint64_t b_req) {  // after the request of buffer b_req: position records for b_req + 1, map word for b_req + 4
+        if (ONE_COPY) wc = w0;
+        else hnext = a.td_rec[locate(w0)];
         w0 = w1;
         w1 = w2;
         w2 = head[b_req + 4];
     };
-    auto request = [&](uint64_t b, Stage& S) {  // uses hnext = record of buffer b
+    auto request = [&](uint64_t b, Stage& S) {  // uses hnext = record of buffer b (ONE_COPY: wc = its head word)
+        if (ONE_COPY) {
+            const uint32_t idx = locate(wc);  // ascends with the lane by at most 63 over a buffer: a tile from lane 0's record on holds them all
+            if (__builtin_expect(__ballot(idx - td0 >= (uint32_t)CLS_TILE) != 0ull, 0)) tile_td((uint32_t)__builtin_amdgcn_readfirstlane((int)idx));
+            const u32x4 r = s_td[idx - td0];
+            hnext.prefix = r.x;
+            hnext.qpos = r.y;
+            hnext.off = (uint64_t)r.z | ((uint64_t)r.w << 32);
+        }
         // (lanes past the call's last hit stay on the last record and run up to 63 entries past its run: still inside the table
         //  allocation -- the engine keeps a page of slack behind it -- and their verdict is discarded)
         const uint64_t entry = hnext.off + (uint64_t)((uint32_t)(b << 6) + (uint32_t)lane - hnext.prefix);  // run offset + index inside the run
@@ -1064,18 +1137,31 @@ __global__ __launch_bounds__(CTX_THREADS_MAX, 8) void extend_filter_cls_kernel(E
         if (ONE_COPY) {
             // copy 0: dword j holds bases [16 j, 16 j + 16), base 16 j + k in bits 2k, 2k + 1; the window at position p is the bit string
             // from bit 2 (p & 15) of dword p >> 4 on: one more dword per side and a funnel shift per dword
-            uint4 t;
-            uint32_t t4;
-            const uint8_t* rpp = a.q2_own + ((query_loc >> 4) << 2);
-            __builtin_memcpy(&t, __builtin_assume_aligned(rpp, 4), 16);
-            __builtin_memcpy(&t4, __builtin_assume_aligned(rpp + 16, 4), 4);
-            const uint32_t sr = (query_loc & 15u) << 1;
-            uint4 u;
-            uint32_t u4;
-            const uint8_t* lpp = a.q2_other + ((lp >> 4) << 2);
-            __builtin_memcpy(&u, __builtin_assume_aligned(lpp, 4), 16);
-            __builtin_memcpy(&u4, __builtin_assume_aligned(lpp + 16, 4), 4);
-            const uint32_t sl = (lp & 15u) << 1;
+            uint4 t, u;
+            uint32_t t4, u4;
+            const uint32_t dr = query_loc >> 4, dl = lp >> 4;
+            const uint32_t sr = (query_loc & 15u) << 1, sl = (lp & 15u) << 1;
+            bool tiled = true;  // wave-uniform
+            if (__builtin_expect(__ballot(dr - dr0 > CLS_WIN_SPAN || dl - dl0 > CLS_WIN_SPAN) != 0ull, 0)) {
+                tile_q((uint32_t)__builtin_amdgcn_readfirstlane((int)dr), (uint32_t)__builtin_amdgcn_readfirstlane((int)dl));
+                tiled = __ballot(dr - dr0 > CLS_WIN_SPAN || dl - dl0 > CLS_WIN_SPAN) == 0ull;
+            }
+            if (tiled) {
+                const LdsU32 rp = s_qr + (dr - dr0), lq = s_ql + (dl - dl0);
+                t = make_uint4(rp[0], rp[1], rp[2], rp[3]);
+                t4 = rp[4];
+                u = make_uint4(lq[0], lq[1], lq[2], lq[3]);
+                u4 = lq[4];
+            } else {
+                const uint8_t* rpp = a.q2_own + (dr << 2);
+                __builtin_memcpy(&t, __builtin_assume_aligned(rpp, 4), 16);
+                __builtin_memcpy(&t4, __builtin_assume_aligned(rpp + 16, 4), 4);
+                const uint8_t* lpp = a.q2_other + (dl << 2);
+                __builtin_memcpy(&u, __builtin_assume_aligned(lpp, 4), 16);
+                __builtin_memcpy(&u4, __builtin_assume_aligned(lpp + 16, 4), 4);
+                // (vmcnt(0): loads that are in flight on ONE side of a join make the waits behind it drains on both; this side is the rare one)
+                __builtin_amdgcn_s_waitcnt(0x0F70);
+            }
             merge_q(S, __builtin_amdgcn_alignbit(t.y, t.x, sr), __builtin_amdgcn_alignbit(t.z, t.y, sr), __builtin_amdgcn_alignbit(t.w, t.z, sr),
                     __builtin_amdgcn_alignbit(t4, t.w, sr), __builtin_amdgcn_alignbit(u.y, u.x, sl), __builtin_amdgcn_alignbit(u.z, u.y, sl),
                     __builtin_amdgcn_alignbit(u.w, u.z, sl), __builtin_amdgcn_alignbit(u4, u.w, sl));
@@ -1159,11 +1245,11 @@ __global__ __launch_bounds__(CTX_THREADS_MAX, 8) void extend_filter_cls_kernel(E
             uint2 ar;
             ar.x = ref_loc;
             ar.y = query_loc;
-            wave_append(valid && !skip && !fwd, ar, a.audit_list, a.audit_count, a.audit_cap, lane, lane_lt);
+            wave_append(valid && !skip && !fwd, ar, a.audit_list, a.audit_count, a.audit_cap, lane, (1ull << rare_lane()) - 1ull);
         }
     };
     // Software pipeline, two register sets: while buffer b is scored the records and query windows of buffer b + 1 are in
-    // flight, the position-record gather of b + 2 and the map word of b + 5.  A wave alone keeps only one buffer's loads in flight;
+    // flight, the position-record gather of b + 2 (sixteen-copy form only) and the map word of b + 5.  A wave alone keeps only one buffer's loads in flight;
     // at 8 waves per SIMD that left the kernel waiting for memory latency (half the record bytes: -9 %; 12 % fewer VALU
     // instructions: -0 %), not for bandwidth or issue slots.
     Stage SA, SB;
@@ -1173,19 +1259,30 @@ __global__ __launch_bounds__(CTX_THREADS_MAX, 8) void extend_filter_cls_kernel(E
         w1 = head[b_lo + 2];
         w2 = head[b_lo + 3];
         cbefore = a.td_chunk[c_lo] + 1u - (uint32_t)(h0 & 1ull);
-        hnext = a.td_rec[locate(h0)];
+        if (ONE_COPY) {  // the wave's first tiles, from the record of its first hit on
+            const uint32_t i0 = a.td_chunk[c_lo];
+            const uint32_t ql0 = a.td_rec[i0].qpos + a.seed_size;
+            wc = h0;
+            tile_td(i0);
+            tile_q(ql0 >> 4, (a.query_len - ql0 + a.left_skip) >> 4);
+        } else {
+            hnext = a.td_rec[locate(h0)];
+        }
         request(b_lo, SA);
         advance_map(b_lo);  // hnext = record of b_lo + 1
     }
-    for (uint64_t b = b_lo; b < b_hi; b += 2) {
+    // (whole pairs in the loop, an odd last buffer behind it: an exit in the middle of the body is laid out as a block that falls into the
+    //  loop's head with SB's loads in flight, and the head then waits for every load before it requests anything)
+    uint64_t b = b_lo;
+    for (; b + 1 < b_hi; b += 2) {
         request(b + 1, SB);
         advance_map(b + 1);
         score(b, SA);
-        if (b + 1 >= b_hi) break;
         request(b + 2, SA);
         advance_map(b + 2);
         score(b + 1, SB);
     }
+    if (b < b_hi) score(b, SA);
     stage_flush(stage, n_stage, my_list, my_count, a.l2_cap, lane);
 }
 
@@ -1799,10 +1896,20 @@ void launch_extend_filter_cls(const ExtendArgs& a, hipStream_t s) {
     threads = std::min<uint32_t>(CTX_THREADS_MAX, std::max<uint32_t>(64, threads & ~63u));
     const uint32_t wpb = threads / 64;
     const uint32_t blocks = (uint32_t)((waves + wpb - 1) / wpb);
-    const size_t lds = wpb * CTX_STAGE_CAP * sizeof(L2Rec);
+    const bool one_copy = a.cls_one_copy != 2;
+    // forward stage, and behind it the one-copy form's tiles: 54 KB of dynamic LDS for sixteen waves next to the 17 KB class table,
+    // above the 64 KB a launch gets without being asked; two workgroups still share a CU's 160 KB
+    const size_t lds = wpb * (CTX_STAGE_CAP * sizeof(L2Rec) + (one_copy ? (size_t)CLS_TILE_BYTES : 0));
+    static std::atomic<size_t> cls_lds_set[64];  // per device ordinal, as for the chain sort below
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (one_copy && lds > 32 * 1024 && dev >= 0 && dev < 64 && cls_lds_set[dev].load(std::memory_order_acquire) < lds) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&extend_filter_cls_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        size_t seen = cls_lds_set[dev].load(std::memory_order_relaxed);
+        while (seen < lds && !cls_lds_set[dev].compare_exchange_weak(seen, lds, std::memory_order_release)) {}
+    }
     // the query windows out of ONE copy (see the kernel): -24 % on the kernel with ~5 hits per position, no loss with ~78 (the default
     // workload measures the same either way, same box); option cls_one_copy = 2 keeps the sixteen shifted copies (A/B)
-    const bool one_copy = a.cls_one_copy != 2;
     if (one_copy) hipLaunchKernelGGL(extend_filter_cls_kernel<true>, dim3(blocks), dim3(threads), lds, s, a);
     else hipLaunchKernelGGL(extend_filter_cls_kernel<false>, dim3(blocks), dim3(threads), lds, s, a);
 }
