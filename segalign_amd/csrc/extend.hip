@@ -915,11 +915,14 @@ constexpr int CLS_TAB = 4096;                       // 12-bit fields: six bases
 constexpr int CLS_TAIL = 256;                       // the left context ends with a four-base field (64 = 10 x 6 + 4)
 constexpr int CLS_LDS_DWORDS = CLS_TAB + CLS_TAIL;  // 4-byte entries: 16 KB + 1 KB
 constexpr bool CLS_TRACK_DROP = true;               // keep the lowest N seen at a field end (see cls_step)
-// per-wave tiles of the one-copy form (see the kernel): 64 position records and 64 dwords of either strand's unshifted 2-bit copy
+// per-wave tiles of the one-copy form (see the kernel): 32 finished position slots and 64 dwords of either strand's unshifted 2-bit copy
 constexpr int CLS_TILE = 64;
 constexpr int CLS_WIN_DWORDS = 5;                                 // dwords a window takes from the unshifted copy
 constexpr uint32_t CLS_WIN_SPAN = CLS_TILE - CLS_WIN_DWORDS;      // a window may start at tile dwords 0 .. 59
-constexpr int CLS_TILE_BYTES = CLS_TILE * (int)sizeof(TdRec) + 2 * CLS_TILE * 4;  // 1.5 KB per wave
+constexpr int CLS_POS_SLOTS = 32;                                 // positions of the position tile (a power of two)
+constexpr int CLS_POS_SLOT_BYTES = 40;                            // string dwords 0..3 | dwords 4..6, query_loc | record stream base: 16 + 16 + 8
+constexpr int CLS_TILE_BYTES = CLS_POS_SLOTS * CLS_POS_SLOT_BYTES + 2 * CLS_TILE * 4;  // 1.75 KB per wave (at most 2112: two workgroups per CU)
+static_assert((CLS_POS_SLOTS & (CLS_POS_SLOTS - 1)) == 0 && CLS_POS_SLOTS <= 64 && CLS_TILE_BYTES % 16 == 0 && CLS_TILE_BYTES <= 2112, "position tile");
 
 // entry of a field: {sum : sum - mx} as two int16 (sum = score of the field, mx = its largest prefix score, >= 0)
 __device__ __forceinline__ void cls_table_init(uint32_t* __restrict__ s_cls, const int* cls, int nthreads) {
@@ -994,6 +997,17 @@ __device__ __forceinline__ uint32_t cls_seed_state(const ExtendArgs& a) {
 // wave keeps 64 position records and 64 dwords of either strand's copy 0 in LDS (1.5 KB per wave) and a request issues the two record
 // loads alone: vector loads per buffer 7.1 -> 2.1, L1 -> L2 requests -3.5 %, seven more LDS reads per buffer that add no bank
 // conflict (the lanes of a position read one address), +6.7 % on the default pass with six calls in flight.
+// Position tile (profiles/cls_strings): the tiles left the per-position ARITHMETIC in every lane of every buffer -- the
+// window addresses, eight funnel shifts, the merge into the seven-dword string, the 64-bit record offset -- although the string and the
+// record stream's base depend on the position alone and a buffer holds one to three positions.  The TdRec tile is now a tile of 32
+// FINISHED slots (string, anchor, stream address: 40 bytes each, 1.75 KB per wave with the raw window tiles, which only the slot build
+// and the per-lane path of sparse buffers read now).  A request is locate, one slot address, three LDS reads (b128, b128, b64), one
+// 64-bit add and the two record loads; the slots are built 32 at a time in the wave-uniform branch that used to load the TdRec tile.
+// Per launch of 518 M hits, parent -> this: VALU wave-instructions per 64 hits 179.1 -> 151.4, LDS instructions per buffer 28.4 -> 24.7
+// with SQ_LDS_BANK_CONFLICT unchanged, wave cycles -3.2 %, vector loads per buffer 2.10 -> 2.12 (td_rec is read once per 32 positions
+// instead of once per 64); VGPRs 55 -> 52.  Same box, interleaved, five runs each, all ranges apart: the default pass 1.292-1.303 ->
+// 1.317-1.338 Gbp/s, the human-scale pair +3.8 %, lumpy +5.0 %; --notransition (13 positions per buffer, a build every other buffer)
+// inside the parent's spread.
 template <bool ONE_COPY>
 __global__ __launch_bounds__(CTX_THREADS_MAX, 8) void extend_filter_cls_kernel(ExtendArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t s_cls[CLS_LDS_DWORDS];  // 4-byte entry per 6-base class field (16 KB) + the 4-base tail fields (1 KB)
@@ -1027,7 +1041,7 @@ __global__ __launch_bounds__(CTX_THREADS_MAX, 8) void extend_filter_cls_kernel(E
     // VALU per buffer on the same question).  td_chunk gives the count at the wave's first hit.  The map is read through the
     // constant address space: a wave-uniform address there is a SCALAR load (s_load_dwordx2), no VALU or vector-memory slot.
     // Latency: the head word is fetched four buffers ahead, the TdRec gather two and the records one buffer ahead (see the loop); the
-    // one-copy form has no gather stage: its request reads the position records from the wave's tile in LDS.
+    // one-copy form has no gather stage: its request reads the position's finished slot from the wave's tile in LDS.
     // Requests past the wave's range read valid memory (the next wave's buffers, the map's zero words, 16 KB of slack behind the
     // table) and are never used -- conditional loads would turn every s_waitcnt of the loop into a drain.
     typedef const uint64_t __attribute__((address_space(4))) * HeadPtr;
@@ -1046,38 +1060,51 @@ __global__ __launch_bounds__(CTX_THREADS_MAX, 8) void extend_filter_cls_kernel(E
         uint32_t query_loc;
     };
     // the query string out of the two windows: qr = 4 dwords from the anchor on (this strand), ql = 4 dwords of the other strand's window
-    auto merge_q = [&](Stage& S, uint32_t qr0, uint32_t qr1, uint32_t qr2, uint32_t qr3, uint32_t ql0, uint32_t ql1, uint32_t ql2, uint32_t ql3) {
-        S.q[0] = qr0; S.q[1] = qr1; S.q[2] = qr2;
-        S.q[3] = (qr3 & 0xFFFu) | (ql0 << 12);  // bits 96..107: right bases 48..53; from bit 108 on: the left window
-        S.q[4] = __builtin_amdgcn_alignbit(ql1, ql0, 20);
-        S.q[5] = __builtin_amdgcn_alignbit(ql2, ql1, 20);
-        S.q[6] = __builtin_amdgcn_alignbit(ql3, ql2, 20);
+    auto merge_q = [&](uint32_t (&q)[7], uint32_t qr0, uint32_t qr1, uint32_t qr2, uint32_t qr3, uint32_t ql0, uint32_t ql1, uint32_t ql2, uint32_t ql3) {
+        q[0] = qr0; q[1] = qr1; q[2] = qr2;
+        q[3] = (qr3 & 0xFFFu) | (ql0 << 12);  // bits 96..107: right bases 48..53; from bit 108 on: the left window
+        q[4] = __builtin_amdgcn_alignbit(ql1, ql0, 20);
+        q[5] = __builtin_amdgcn_alignbit(ql2, ql1, 20);
+        q[6] = __builtin_amdgcn_alignbit(ql3, ql2, 20);
     };
     uint64_t w0, w1, w2;  // head words of the buffers one, two and three ahead of the one being requested
     uint64_t wc = 0;      // (ONE_COPY) head word of the next buffer to be requested
-    TdRec hnext;          // TdRec of this lane's hit in the NEXT buffer to be requested (ONE_COPY: read from the tile by the request itself)
-    // ONE_COPY: the per-position data come out of three tiles in LDS that belong to the wave alone (no other wave reads or writes
+    TdRec hnext;          // (sixteen-copy form) TdRec of this lane's hit in the NEXT buffer to be requested
+    // ONE_COPY: the per-position data come out of tiles in LDS that belong to the wave alone (no other wave reads or writes
     // them, and the LDS serves a wave's instructions in order, so no barrier is involved):
-    //   s_td  td_rec[td0 .. td0 + 63]                          one 16-byte read per lane, the lanes of a position read one address
-    //   s_qr  dwords dr0 .. dr0 + 63 of this strand's copy 0   five dwords per lane from window dword (query_loc >> 4) - dr0 on
+    //   s_pa, s_pb, s_pc  the POSITION TILE: CLS_POS_SLOTS slots for td_rec[td0 .. td0 + 31], each holding what a request needs,
+    //         FINISHED: the seven-dword query string as merge_q makes it (s_pa: dwords 0..3; s_pb: dwords 4..6 and query_loc) and the
+    //         64-bit address of the position's record stream, ctx + 32 (off - prefix) (s_pc), so that a lane's record lies at
+    //         base + 32 hit.  Three reads per lane (two of 16 bytes, one of 8); the lanes of a position read one address.
+    //   s_qr  dwords dr0 .. dr0 + 63 of this strand's copy 0   the windows of a slot BUILD: five dwords from (query_loc >> 4) - dr0 on
     //   s_ql  the same of the other strand's copy from dl0 on; its positions DESCEND along a call, so a new tile ENDS at its first window
-    // A tile is loaded by ONE coalesced load of the wave (lanes past the end of the array stay on its last element) and lasts until a
-    // buffer has a lane outside it: then the wave loads it anew from that buffer's first lane on, in a wave-uniform branch.  The
-    // straight-line part of the loop holds the record loads alone.  A buffer whose windows spread over more than one tile (positions
-    // more than ~900 bases apart inside 64 hits: sparse calls) takes its windows from memory as the sixteen-copy form does.
+    // The string and the base depend on the position alone, and a buffer holds one to three positions: the shifts, the merge and the
+    // 64-bit offset arithmetic are done once per slot when the tile is built, not in every lane of every buffer.  The position tile
+    // lasts until a buffer has a lane whose record lies outside it: then the wave builds it anew from that buffer's first lane on, in
+    // a wave-uniform branch, lane l making slot l & 31 (td_rec is read by one coalesced load, lanes past the end of the array stay on
+    // its last element).  The build takes its windows from the raw tiles, which are loaded anew -- one coalesced load each -- when a
+    // slot's window lies outside them; a slot whose windows do not fit even then reads them from memory.  The straight-line part of
+    // the loop holds the record loads alone.  A buffer that spans more than 32 positions (sparse calls, few hits per position) makes
+    // its strings per lane, as every buffer did before the position tile.
     // (the tiles are addressed as LDS explicitly: through generic pointers the compiler folds the tile reads and the fallback's reads
     //  from memory into FLAT loads behind a pointer select, and every wait of the loop becomes a drain)
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     typedef u32x4 __attribute__((address_space(3))) * LdsU4;
+    typedef u32x2 __attribute__((address_space(3))) * LdsU2;
     typedef uint32_t __attribute__((address_space(3))) * LdsU32;
-    LdsU4 s_td = nullptr;
+    typedef const u32x4 __attribute__((address_space(1))) * GlobU4;  // (a record address out of an integer stays a GLOBAL load)
+    LdsU4 s_pa = nullptr, s_pb = nullptr;
+    LdsU2 s_pc = nullptr;
     LdsU32 s_qr = nullptr, s_ql = nullptr;
     uint32_t td0 = 0, dr0 = 0, dl0 = 0;
     const uint32_t q2_last = (uint32_t)(a.q2_stride >> 2) - 1u;  // last dword of a copy (q2_copy_stride: Q2_TAIL zero bytes behind the bases)
     if (ONE_COPY) {
         char* tiles = reinterpret_cast<char*>(s_l2_dyn) + (size_t)(blockDim.x >> 6) * (CTX_STAGE_CAP * sizeof(L2Rec)) + (size_t)(threadIdx.x >> 6) * CLS_TILE_BYTES;
-        s_td = (LdsU4)tiles;
-        s_qr = (LdsU32)(tiles + CLS_TILE * sizeof(TdRec));
+        s_pa = (LdsU4)tiles;
+        s_pb = s_pa + CLS_POS_SLOTS;
+        s_pc = (LdsU2)(s_pb + CLS_POS_SLOTS);
+        s_qr = (LdsU32)(s_pc + CLS_POS_SLOTS);
         s_ql = s_qr + CLS_TILE;
     }
     // (rare_lane: the lane number behind an empty asm, so that what the rare paths derive from it -- tile addresses, the audit's lane
@@ -1087,15 +1114,7 @@ __global__ __launch_bounds__(CTX_THREADS_MAX, 8) void extend_filter_cls_kernel(E
         asm volatile("" : "+v"(l));
         return l;
     };
-    auto tile_td = [&](uint32_t base) {  // (td_rec holds td_m + 1 records)
-        const uint32_t l = rare_lane();
-        const TdRec r = a.td_rec[min(base + l, a.td_m)];
-        __builtin_amdgcn_wave_barrier();
-        s_td[l] = u32x4{r.prefix, r.qpos, (uint32_t)r.off, (uint32_t)(r.off >> 32)};
-        __builtin_amdgcn_wave_barrier();
-        td0 = base;
-    };
-    auto tile_q = [&](uint32_t own_dword, uint32_t other_dword) {  // window dwords of the buffer's first lane
+    auto tile_q = [&](uint32_t own_dword, uint32_t other_dword) __attribute__((always_inline)) {  // window dwords of the first lane (of a buffer or of a build)
         const uint32_t nr = own_dword, nl = other_dword > CLS_WIN_SPAN ? other_dword - CLS_WIN_SPAN : 0u;
         const uint32_t l = rare_lane();
         const uint32_t vr = reinterpret_cast<const uint32_t*>(a.q2_own)[min(nr + l, q2_last)];
@@ -1107,6 +1126,58 @@ __global__ __launch_bounds__(CTX_THREADS_MAX, 8) void extend_filter_cls_kernel(E
         dr0 = nr;
         dl0 = nl;
     };
+    // (ONE_COPY, rare paths: a slot build, a per-lane buffer; every lane of the wave takes part)  the query string of the position with
+    // anchor query_loc.  copy 0: dword j holds bases [16 j, 16 j + 16), base 16 j + k in bits 2k, 2k + 1; the window at position p is
+    // the bit string from bit 2 (p & 15) of dword p >> 4 on: five dwords per side and a funnel shift per dword.  The positions of the
+    // lanes ascend, so raw tiles loaded anew at lane 0's windows hold whatever one tile can hold; a lane whose windows still lie
+    // outside reads them from memory.
+    auto make_string = [&](uint32_t query_loc, uint32_t (&q)[7]) __attribute__((always_inline)) {
+        // the left context starts in front of the seed (CtxRec): the other strand's forward window at len - anchor + seed_size
+        const uint32_t lp = a.query_len - query_loc + a.left_skip;
+        const uint32_t dr = query_loc >> 4, dl = lp >> 4;
+        const uint32_t sr = (query_loc & 15u) << 1, sl = (lp & 15u) << 1;
+        if (__ballot(dr - dr0 > CLS_WIN_SPAN || dl - dl0 > CLS_WIN_SPAN) != 0ull)
+            tile_q((uint32_t)__builtin_amdgcn_readfirstlane((int)dr), (uint32_t)__builtin_amdgcn_readfirstlane((int)dl));
+        uint4 t, u;
+        uint32_t t4, u4;
+        if (!(dr - dr0 > CLS_WIN_SPAN || dl - dl0 > CLS_WIN_SPAN)) {
+            const LdsU32 rp = s_qr + (dr - dr0), lq = s_ql + (dl - dl0);
+            t = make_uint4(rp[0], rp[1], rp[2], rp[3]);
+            t4 = rp[4];
+            u = make_uint4(lq[0], lq[1], lq[2], lq[3]);
+            u4 = lq[4];
+        } else {
+            const uint8_t* rpp = a.q2_own + (dr << 2);
+            __builtin_memcpy(&t, __builtin_assume_aligned(rpp, 4), 16);
+            __builtin_memcpy(&t4, __builtin_assume_aligned(rpp + 16, 4), 4);
+            const uint8_t* lpp = a.q2_other + (dl << 2);
+            __builtin_memcpy(&u, __builtin_assume_aligned(lpp, 4), 16);
+            __builtin_memcpy(&u4, __builtin_assume_aligned(lpp + 16, 4), 4);
+            // (vmcnt(0): loads that are in flight on ONE side of a join make the waits behind it drains on both; this side is the rare one)
+            __builtin_amdgcn_s_waitcnt(0x0F70);
+        }
+        merge_q(q, __builtin_amdgcn_alignbit(t.y, t.x, sr), __builtin_amdgcn_alignbit(t.z, t.y, sr), __builtin_amdgcn_alignbit(t.w, t.z, sr),
+                __builtin_amdgcn_alignbit(t4, t.w, sr), __builtin_amdgcn_alignbit(u.y, u.x, sl), __builtin_amdgcn_alignbit(u.z, u.y, sl),
+                __builtin_amdgcn_alignbit(u.w, u.z, sl), __builtin_amdgcn_alignbit(u4, u.w, sl));
+    };
+    // address of the record stream of a position: entry off + (hit - prefix) of the table, 32 bytes each, with off - prefix folded in
+    auto stream_base = [&](const TdRec& r) -> uint64_t { return reinterpret_cast<uint64_t>(ctx) + ((r.off - (uint64_t)r.prefix) << 5); };
+    auto tile_pos = [&](uint32_t base) __attribute__((always_inline)) {  // slots for td_rec[base .. base + 31] (td_rec holds td_m + 1 records); lanes 32..63 repeat 0..31
+        const uint32_t l = rare_lane();
+        const TdRec r = a.td_rec[min(base + (l & (uint32_t)(CLS_POS_SLOTS - 1)), a.td_m)];
+        const uint32_t query_loc = r.qpos + a.seed_size;  // :204
+        uint32_t q[7];
+        make_string(query_loc, q);
+        const uint64_t rb = stream_base(r);
+        __builtin_amdgcn_wave_barrier();
+        if (l < (uint32_t)CLS_POS_SLOTS) {
+            s_pa[l] = u32x4{q[0], q[1], q[2], q[3]};
+            s_pb[l] = u32x4{q[4], q[5], q[6], query_loc};
+            s_pc[l] = u32x2{(uint32_t)rb, (uint32_t)(rb >> 32)};
+        }
+        __builtin_amdgcn_wave_barrier();
+        td0 = base;
+    };
     auto advance_map = [&](uint64_t b_req) {  // after the request of buffer b_req: position records for b_req + 1, map word for b_req + 4
         if (ONE_COPY) wc = w0;
         else hnext = a.td_rec[locate(w0)];
@@ -1116,15 +1187,39 @@ __global__ __launch_bounds__(CTX_THREADS_MAX, 8) void extend_filter_cls_kernel(E
     };
     auto request = [&](uint64_t b, Stage& S) {  // uses hnext = record of buffer b (ONE_COPY: wc = its head word)
         if (ONE_COPY) {
-            const uint32_t idx = locate(wc);  // ascends with the lane by at most 63 over a buffer: a tile from lane 0's record on holds them all
-            if (__builtin_expect(__ballot(idx - td0 >= (uint32_t)CLS_TILE) != 0ull, 0)) tile_td((uint32_t)__builtin_amdgcn_readfirstlane((int)idx));
-            const u32x4 r = s_td[idx - td0];
-            hnext.prefix = r.x;
-            hnext.qpos = r.y;
-            hnext.off = (uint64_t)r.z | ((uint64_t)r.w << 32);
+            const uint32_t idx = locate(wc);  // ascends with the lane
+            bool slots = true;                // wave-uniform: the position tile holds every lane's record
+            if (__builtin_expect(__ballot(idx - td0 >= (uint32_t)CLS_POS_SLOTS) != 0ull, 0)) {
+                tile_pos((uint32_t)__builtin_amdgcn_readfirstlane((int)idx));
+                slots = __ballot(idx - td0 >= (uint32_t)CLS_POS_SLOTS) == 0ull;
+            }
+            uint64_t rb;
+            if (__builtin_expect(slots, 1)) {
+                const uint32_t k = idx - td0;
+                const u32x4 qa = s_pa[k], qb = s_pb[k];
+                const u32x2 pc = s_pc[k];
+                S.q[0] = qa.x; S.q[1] = qa.y; S.q[2] = qa.z; S.q[3] = qa.w;
+                S.q[4] = qb.x; S.q[5] = qb.y; S.q[6] = qb.z;
+                S.query_loc = qb.w;
+                rb = (uint64_t)pc.x | ((uint64_t)pc.y << 32);
+            } else {  // more than CLS_POS_SLOTS positions in 64 hits: per lane, as the build does it per slot
+                const TdRec r = a.td_rec[min(idx, a.td_m)];
+                S.query_loc = r.qpos + a.seed_size;  // :204
+                make_string(S.query_loc, S.q);
+                rb = stream_base(r);
+                __builtin_amdgcn_s_waitcnt(0x0F70);  // (nothing of this side in flight at the join, see make_string)
+            }
+            // (lanes past the call's last hit stay on the last record and run up to 63 entries past its run: still inside the table
+            //  allocation -- the engine keeps a page of slack behind it -- and their verdict is discarded)
+            // 32 x hit: the buffer's part is scalar and a multiple of 2048, the lane's part lies below it
+            const uint64_t at = ((uint64_t)(uint32_t)(b << 6) << 5) | (uint64_t)((uint32_t)lane << 5);
+            const GlobU4 rec = (GlobU4)(rb + at);
+            const u32x4 c0 = rec[0], tl = rec[1];  // two aligned 16-byte loads: the stream of the kernel
+            S.c0 = make_uint4(c0.x, c0.y, c0.z, c0.w);
+            S.tl = make_uint4(tl.x, tl.y, tl.z, tl.w);
+            return;
         }
-        // (lanes past the call's last hit stay on the last record and run up to 63 entries past its run: still inside the table
-        //  allocation -- the engine keeps a page of slack behind it -- and their verdict is discarded)
+        // sixteen-copy form (lanes past the call's last hit: as above)
         const uint64_t entry = hnext.off + (uint64_t)((uint32_t)(b << 6) + (uint32_t)lane - hnext.prefix);  // run offset + index inside the run
         S.c0 = ctx[2 * entry];  // two aligned 16-byte loads: the stream of the kernel
         S.tl = ctx[2 * entry + 1];  // (28-byte records were measured in round 5 and lost: profiles/r05/exp_rec28.txt)
@@ -1134,45 +1229,12 @@ __global__ __launch_bounds__(CTX_THREADS_MAX, 8) void extend_filter_cls_kernel(E
         // the offset is ONE 32-bit value next to a scalar base
         // the left context starts in front of the seed (CtxRec): the other strand's forward window at len - anchor + seed_size
         const uint32_t lp = a.query_len - query_loc + a.left_skip;
-        if (ONE_COPY) {
-            // copy 0: dword j holds bases [16 j, 16 j + 16), base 16 j + k in bits 2k, 2k + 1; the window at position p is the bit string
-            // from bit 2 (p & 15) of dword p >> 4 on: one more dword per side and a funnel shift per dword
-            uint4 t, u;
-            uint32_t t4, u4;
-            const uint32_t dr = query_loc >> 4, dl = lp >> 4;
-            const uint32_t sr = (query_loc & 15u) << 1, sl = (lp & 15u) << 1;
-            bool tiled = true;  // wave-uniform
-            if (__builtin_expect(__ballot(dr - dr0 > CLS_WIN_SPAN || dl - dl0 > CLS_WIN_SPAN) != 0ull, 0)) {
-                tile_q((uint32_t)__builtin_amdgcn_readfirstlane((int)dr), (uint32_t)__builtin_amdgcn_readfirstlane((int)dl));
-                tiled = __ballot(dr - dr0 > CLS_WIN_SPAN || dl - dl0 > CLS_WIN_SPAN) == 0ull;
-            }
-            if (tiled) {
-                const LdsU32 rp = s_qr + (dr - dr0), lq = s_ql + (dl - dl0);
-                t = make_uint4(rp[0], rp[1], rp[2], rp[3]);
-                t4 = rp[4];
-                u = make_uint4(lq[0], lq[1], lq[2], lq[3]);
-                u4 = lq[4];
-            } else {
-                const uint8_t* rpp = a.q2_own + (dr << 2);
-                __builtin_memcpy(&t, __builtin_assume_aligned(rpp, 4), 16);
-                __builtin_memcpy(&t4, __builtin_assume_aligned(rpp + 16, 4), 4);
-                const uint8_t* lpp = a.q2_other + (dl << 2);
-                __builtin_memcpy(&u, __builtin_assume_aligned(lpp, 4), 16);
-                __builtin_memcpy(&u4, __builtin_assume_aligned(lpp + 16, 4), 4);
-                // (vmcnt(0): loads that are in flight on ONE side of a join make the waits behind it drains on both; this side is the rare one)
-                __builtin_amdgcn_s_waitcnt(0x0F70);
-            }
-            merge_q(S, __builtin_amdgcn_alignbit(t.y, t.x, sr), __builtin_amdgcn_alignbit(t.z, t.y, sr), __builtin_amdgcn_alignbit(t.w, t.z, sr),
-                    __builtin_amdgcn_alignbit(t4, t.w, sr), __builtin_amdgcn_alignbit(u.y, u.x, sl), __builtin_amdgcn_alignbit(u.z, u.y, sl),
-                    __builtin_amdgcn_alignbit(u.w, u.z, sl), __builtin_amdgcn_alignbit(u4, u.w, sl));
-        } else {
-            const uint32_t po = (mul24(query_loc & 15u, stride16) << 4) + ((query_loc >> 4) << 2);
-            uint4 t, u;
-            __builtin_memcpy(&t, __builtin_assume_aligned(a.q2_own + po, 4), 16);
-            const uint32_t qo = (mul24(lp & 15u, stride16) << 4) + ((lp >> 4) << 2);
-            __builtin_memcpy(&u, __builtin_assume_aligned(a.q2_other + qo, 4), 16);
-            merge_q(S, t.x, t.y, t.z, t.w, u.x, u.y, u.z, u.w);
-        }
+        const uint32_t po = (mul24(query_loc & 15u, stride16) << 4) + ((query_loc >> 4) << 2);
+        uint4 t, u;
+        __builtin_memcpy(&t, __builtin_assume_aligned(a.q2_own + po, 4), 16);
+        const uint32_t qo = (mul24(lp & 15u, stride16) << 4) + ((lp >> 4) << 2);
+        __builtin_memcpy(&u, __builtin_assume_aligned(a.q2_other + qo, 4), 16);
+        merge_q(S.q, t.x, t.y, t.z, t.w, u.x, u.y, u.z, u.w);
     };
     auto score = [&](uint64_t b, const Stage& S) {
         const bool valid = (b << 6) + (uint64_t)lane < a.num_hits;
@@ -1263,8 +1325,8 @@ __global__ __launch_bounds__(CTX_THREADS_MAX, 8) void extend_filter_cls_kernel(E
             const uint32_t i0 = a.td_chunk[c_lo];
             const uint32_t ql0 = a.td_rec[i0].qpos + a.seed_size;
             wc = h0;
-            tile_td(i0);
             tile_q(ql0 >> 4, (a.query_len - ql0 + a.left_skip) >> 4);
+            tile_pos(i0);
         } else {
             hnext = a.td_rec[locate(h0)];
         }
@@ -1897,8 +1959,8 @@ void launch_extend_filter_cls(const ExtendArgs& a, hipStream_t s) {
     const uint32_t wpb = threads / 64;
     const uint32_t blocks = (uint32_t)((waves + wpb - 1) / wpb);
     const bool one_copy = a.cls_one_copy != 2;
-    // forward stage, and behind it the one-copy form's tiles: 54 KB of dynamic LDS for sixteen waves next to the 17 KB class table,
-    // above the 64 KB a launch gets without being asked; two workgroups still share a CU's 160 KB
+    // forward stage, and behind it the one-copy form's tiles: 58 KB of dynamic LDS for sixteen waves next to the 17 KB class table,
+    // above the 64 KB a launch gets without being asked; two workgroups still share a CU's 160 KB (CLS_TILE_BYTES <= 2112)
     const size_t lds = wpb * (CTX_STAGE_CAP * sizeof(L2Rec) + (one_copy ? (size_t)CLS_TILE_BYTES : 0));
     static std::atomic<size_t> cls_lds_set[64];  // per device ordinal, as for the chain sort below
     int dev = 0;
