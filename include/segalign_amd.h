@@ -1670,6 +1670,106 @@ size_t sa_lift_intervals(const uint32_t* first, const uint32_t* block_start, con
                          sa_lift_block** blocks, size_t* n_blocks, sa_lift_stats* stats);
 void sa_free_lift(sa_lift_record* records, sa_lift_hit* hits, sa_lift_block* blocks);
 
+/* ---- differences and identity of alignments (additive) -------------------------------------------
+ *
+ * sa_diff_alignments reads alignments back against the two resident sequences: where they differ (events), what each alignment is made
+ * of (one summary per alignment) and the pair counts over all aligned columns.  It is the project's own contract in the spirit of
+ * LASTZ's --format=differences and is not claimed to equal it.  tests/diff_model.py restates it by plain column expansion,
+ * tests/cpp/diff_check.c serially without expanding.  The entry needs a resident target block and query buffer, like
+ * sa_stitch_chains, whose errors it gives without one.
+ *   Input: n <= 1 << 22 spans and an array of n_ops_total <= 1 << 28 ops, uint32 (run << 2) | op with SA_GAPPED_OP_M / _I / _D, the
+ *     encoding sa_gapped_align, sa_gapped_align_greedy and sa_stitch_chains write.  Span k's ops are ops[op_offset .. op_offset + n_ops).
+ *     Its columns are these entries expanded in order: from (ref_start, query_start), an M column consumes one base of each sequence,
+ *     an I column a query base and a D column a target base.  A span with n_ops = 0 is legal and empty.  Adjacent entries with the same
+ *     op are legal: sa_gapped_align leaves them at the anchor and sa_stitch_chains at a run cut at (1 << 30) - 1.
+ *   Validation (on the host in one linear pass; a message and exit code 1, like the other entries), in this order: n and n_ops_total
+ *     within the limits; the op ranges ascend and are disjoint, op_offset[k] + n_ops[k] <= op_offset[k + 1], the last one inside the
+ *     array (every producer satisfies this); no op code 3 and no zero run in a span's ops; every span consumes only bases inside the
+ *     block on both sequences (computed in 64 bits); every span has fewer than 2^32 columns; chunk is 0 (= 4096) or a power of two in
+ *     64 .. 65 536; no unknown flag.  A call whose columns make more than 1 << 30 work items (an M entry of run L is ceil(L / chunk)
+ *     items, a gap entry one) ends with a message too.
+ *   Column classes, from x = T[r] & 7 and y = Q[q] & 7 (A 0, C 1, G 2, T 3, soft-masked 4, N 5, X 6, separator 7) of an M column:
+ *     MATCH x == y and x < 4; TS x, y < 4 and x ^ y == 2; TV x, y < 4 otherwise; OTHER x >= 4 or y >= 4.  So matches is the
+ *     existing entries' matches and TS + TV + OTHER their mismatches.  The resident codes do not keep the base under a soft-masked
+ *     code, so such columns are OTHER.
+ *   Column kinds: a MATCH column has none; TS and TV columns SA_DIFF_SUB; OTHER columns SA_DIFF_OTHER; an I column SA_DIFF_INS; a D
+ *     column SA_DIFF_DEL.
+ *   Events: an event is a maximal run of consecutive columns of one span with the same kind.  A run crosses op-entry boundaries (two
+ *     adjacent I entries are one INS event, a mismatch run over two adjacent M entries is one SUB event) and never a span boundary.
+ *     SUB next to OTHER next to SUB is three events; TS next to TV is one.  With SA_DIFF_PER_BASE every SUB column is its own event of
+ *     length 1 and the other kinds stay runs.  With SA_DIFF_NO_EVENTS no event is returned (the emit pass does not run); summaries,
+ *     their n_events and first_event included, the statistics and the pair counts are what they are without the flag.
+ *   Output: the events ordered by span and then by column.  ref_pos / query_pos: the next base of each sequence at the event's first
+ *     column (for an INS the target base the insertion sits in front of); column: the first column's index in the span; tcode / qcode:
+ *     the codes at the first column, SA_DIFF_NO_CODE on the side an INS / DEL does not consume.  One sa_diff_summary per span:
+ *     first_event is the number of events of all earlier spans, columns = matches + transitions + transversions + others + ins_bases +
+ *     del_bases.  ins_runs / del_runs are counted as events are, that is, merged across adjacent entries: a gapped record's gap_opens
+ *     can therefore exceed ins_runs + del_runs by the gap runs that meet at its anchor (a stitch record's gap_opens equals the sum).
+ *     pairs[tcode * 8 + qcode] counts every M column of every span.  2^31 or more events end the call with a message.
+ * Device side (diff.hip): a prepare step places every op entry, a count pass finds event starts and ends with one wavefront per work
+ * item, prefix sums order them, an emit pass writes them: no sort, and no atomics but the integer adds of the pair counts. */
+#define SA_DIFF_PER_BASE 1u  /* every SUB column is its own event */
+#define SA_DIFF_NO_EVENTS 2u /* summaries, statistics and pair counts only */
+#define SA_DIFF_SUB 0u
+#define SA_DIFF_OTHER 1u
+#define SA_DIFF_INS 2u
+#define SA_DIFF_DEL 3u
+#define SA_DIFF_NO_CODE 8u
+
+typedef struct sa_diff_span { /* 24 bytes */
+    uint32_t ref_start, query_start; /* the bases its first column starts from */
+    uint64_t op_offset;              /* index of its first op */
+    uint32_t n_ops, pad;
+} sa_diff_span;
+
+typedef struct sa_diff_params {
+    uint32_t flags; /* SA_DIFF_PER_BASE | SA_DIFF_NO_EVENTS */
+    uint32_t chunk; /* M columns of one work item: 0 (= 4096) or a power of two in 64 .. 65 536 */
+} sa_diff_params;
+
+typedef struct sa_diff_event { /* 24 bytes */
+    uint32_t span, ref_pos, query_pos, len, column;
+    uint8_t kind, tcode, qcode, pad;
+} sa_diff_event;
+
+typedef struct sa_diff_summary { /* 48 bytes, one per span */
+    uint64_t first_event;
+    uint32_t n_events, columns, matches, transitions, transversions, others, ins_runs, ins_bases, del_runs, del_bases;
+} sa_diff_summary;
+
+typedef struct sa_diff_stats {
+    uint64_t spans;
+    uint64_t ops;        /* op entries of all spans */
+    uint64_t columns;    /* of all spans */
+    uint64_t work_items;
+    uint64_t events;
+    uint64_t pairs[64];  /* M columns by tcode * 8 + qcode */
+    float prep_ms;       /* device time of the prepare step */
+    float count_ms;      /* of the count pass, its prefix sums and the summaries */
+    float emit_ms;       /* of the emit pass */
+    float pad;
+} sa_diff_stats;
+#ifdef __cplusplus
+static_assert(sizeof(sa_diff_span) == 24, "sa_diff_span is 24 bytes");
+static_assert(sizeof(sa_diff_params) == 8, "sa_diff_params is 8 bytes");
+static_assert(sizeof(sa_diff_event) == 24, "sa_diff_event is 24 bytes");
+static_assert(sizeof(sa_diff_summary) == 48, "sa_diff_summary is 48 bytes");
+static_assert(sizeof(sa_diff_stats) == 568, "sa_diff_stats is 568 bytes");
+#else
+_Static_assert(sizeof(sa_diff_span) == 24, "sa_diff_span is 24 bytes");
+_Static_assert(sizeof(sa_diff_params) == 8, "sa_diff_params is 8 bytes");
+_Static_assert(sizeof(sa_diff_event) == 24, "sa_diff_event is 24 bytes");
+_Static_assert(sizeof(sa_diff_summary) == 48, "sa_diff_summary is 48 bytes");
+_Static_assert(sizeof(sa_diff_stats) == 568, "sa_diff_stats is 568 bytes");
+#endif
+
+/* Returns the number of events in *events (0 with SA_DIFF_NO_EVENTS).  *events and *summaries (n of them) are malloc-ed and released
+ * with sa_free_diff; each is NULL when it would be empty.  p: NULL takes the defaults; stats: nullable.  Slots, thread safety and exit
+ * behaviour are those of sa_stitch_chains. */
+size_t sa_diff_alignments(const sa_diff_span* spans, size_t n, const uint32_t* ops, size_t n_ops_total, int rev, uint32_t buffer,
+                          const sa_diff_params* p, sa_diff_event** events, sa_diff_summary** summaries, sa_diff_stats* stats);
+void sa_free_diff(sa_diff_event* events, sa_diff_summary* summaries);
+
 const char* sa_version(void);
 
 #ifdef __cplusplus

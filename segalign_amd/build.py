@@ -12,7 +12,7 @@ SOURCES = ["encode.hip", "scan.hip", "table.hip", "seeds.hip", "probe.hip", "ext
            "api_introspect.hip", "gapped.hip", "cover.hip", "api_gapped.hip", "hspchain.hip", "hsppeel.hip", "hspovl.hip", "api_hspchain.hip",
            "stitch.hip", "api_stitch.hip", "chaintrim.hip", "api_chaintrim.hip", "net.hip", "api_net.hip", "netsubset.hip",
            "api_netsubset.hip", "netclass.hip", "api_netclass.hip", "lift.hip", "api_lift.hip", "fill.hip",
-           "api_fill.hip"]
+           "api_fill.hip", "diff.hip", "api_diff.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 
 

@@ -18,6 +18,7 @@
 //   api_netsubset.hip  sa_net_subset: the fills of a net cut into clipped, rescored sub-chains (netsubset.hip)
 //   api_netclass.hip   sa_net_classify: the fills of a net classed against their parents on the other axis, with duplication and the filter (netclass.hip)
 //   api_lift.hip       sa_lift_intervals: intervals of one axis carried through chains to the other axis (lift.hip)
+//   api_diff.hip       sa_diff_alignments: the differences, summaries and pair counts of alignments (diff.hip)
 //   api_fill.hip       sa_fill_chains: the links of chains filled with HSPs from a sweep of every diagonal (fill.hip)
 //   post_host.h        what those entries and api_chaintrim.hip share on the host: event timing, checked launches and copies, buffer carving,
 //                      caller-owned arrays, trace batches
@@ -370,6 +371,9 @@ struct Slot {
     // sa_lift_intervals (api_lift.hip, lift.hip): the chains, the intervals and what is made per interval; the hits; the output blocks
     DevBuf<uint8_t> lift, lift_hits, lift_out;
     DevBuf<uint8_t> fill;             // sa_fill_chains (api_fill.hip, fill.hip): a batch's tasks, counts and offsets, and an emit group's HSPs
+    // sa_diff_alignments (api_diff.hip, diff.hip): the spans, the ops and what the prepare step makes per op; the work items with their
+    // counts and offsets and the summaries; the events
+    DevBuf<uint8_t> diff, diff_items, diff_out;
     bool early = false;               // taken from the pool that serves sa_chain_hsps before InitializeProcessor (pool.hip)
 };
 

@@ -142,6 +142,9 @@ void slot_destroy(Slot& s) {
     s.lift_hits.release("lift hits");
     s.lift_out.release("lift blocks");
     s.fill.release("fill");
+    s.diff.release("diff");
+    s.diff_items.release("diff items");
+    s.diff_out.release("diff events");
     s.cand_list.release("candidate list");
     s.l2_list.release("second-level list");
     s.audit.release("audit list");

@@ -1,6 +1,7 @@
 // post_checks.h -- the input rules that the post-processing entries share, written once: chains in CSR form, their
-// member HSPs, block pairs on two axes and the head of the fill rules, each with the message its entry prints (tests/test_post_checks.py
-// pins every one of them).  Host code only and free of HIP: include/segalign_amd.h and the standard library, so a plain g++ compiles it.
+// member HSPs, block pairs on two axes, the head of the fill rules and the spans of sa_diff_alignments, each with the message its entry
+// prints (tests/test_post_checks.py and tests/test_diff_model.py pin every one of them).  Host code only and free of HIP:
+// include/segalign_amd.h and the standard library, so a plain g++ compiles it.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -86,6 +87,50 @@ inline void checked_fill_in_chain(const Fail& fail, const sa_net_fill& f, size_t
     if (f.chain >= n_chains) fail("fill %lld names chain %lld, which is not in the input", (long long)k, f.chain);
     if (f.n_blocks < 1 || f.first_block < first[f.chain] || (uint64_t)f.first_block + f.n_blocks > first[f.chain + 1])
         fail("fill %lld: its blocks leave chain %lld", (long long)k, f.chain);
+}
+
+// The limits of sa_diff_alignments.
+constexpr uint32_t DIFF_MAX_SPANS = 1u << 22;
+constexpr uint32_t DIFF_MAX_OPS = 1u << 28;
+constexpr uint32_t DIFF_DEFAULT_CHUNK = 4096;
+
+struct SpanTotals {
+    uint64_t ops, columns;  // over all spans
+};
+
+// The rules of sa_diff_alignments in the contract's order: the counts; the op ranges, ascending and disjoint inside the array; then per
+// span its op codes and runs, its place inside the block of ref_len by query_len bases and its columns; chunk (0 = the default); flags.
+inline SpanTotals checked_spans(const Fail& fail, const sa_diff_span* spans, size_t n, const uint32_t* ops, size_t n_ops_total, uint32_t ref_len,
+                                uint32_t query_len, uint32_t flags, uint32_t chunk) {
+    if (n > DIFF_MAX_SPANS) fail("%lld spans: at most 1 << 22", (long long)n);
+    if (n_ops_total > DIFF_MAX_OPS) fail("%lld ops: at most 1 << 28", (long long)n_ops_total);
+    for (size_t k = 0; k < n; k++) {
+        const uint64_t end = spans[k].op_offset + spans[k].n_ops;
+        if (end < spans[k].op_offset || end > (k + 1 < n ? spans[k + 1].op_offset : (uint64_t)n_ops_total)) {
+            if (k + 1 < n) fail("span %lld: its ops overlap those of span %lld or lie behind them", (long long)k, (long long)(k + 1));
+            fail("span %lld: its ops leave the array of %lld", (long long)k, (long long)n_ops_total);
+        }
+    }
+    SpanTotals t = {0, 0};
+    for (size_t k = 0; k < n; k++) {
+        const sa_diff_span& s = spans[k];
+        uint64_t r = s.ref_start, q = s.query_start, cols = 0;
+        for (uint64_t e = s.op_offset; e < s.op_offset + s.n_ops; e++) {
+            const uint32_t op = ops[e] & 3u, run = ops[e] >> 2;
+            if (op == 3u) fail("span %lld: op %lld has code 3", (long long)k, (long long)(e - s.op_offset));
+            if (run == 0) fail("span %lld: op %lld has a zero run", (long long)k, (long long)(e - s.op_offset));
+            if (op != SA_GAPPED_OP_I) r += run;
+            if (op != SA_GAPPED_OP_D) q += run;
+            cols += run;
+        }
+        if (r > ref_len || q > query_len) fail("span %lld does not lie inside the block", (long long)k);
+        if (cols >= ((uint64_t)1 << 32)) fail("span %lld has %lld columns: fewer than 2^32", (long long)k, (long long)cols);
+        t.ops += s.n_ops;
+        t.columns += cols;
+    }
+    if (chunk != 0 && (chunk < 64 || chunk > 65536 || (chunk & (chunk - 1)))) fail("chunk = %lld: 0 or a power of two in 64 .. 65536", chunk);
+    if (flags & ~(SA_DIFF_PER_BASE | SA_DIFF_NO_EVENTS)) fail("flags = %lld: unknown bits", flags);
+    return t;
 }
 
 }  // namespace sa

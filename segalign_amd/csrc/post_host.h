@@ -1,5 +1,5 @@
-// post_host.h -- the host helpers that the nine post-processing units share (api_gapped.hip, api_hspchain.hip, api_stitch.hip,
-// api_chaintrim.hip, api_fill.hip, api_net.hip, api_netsubset.hip, api_netclass.hip, api_lift.hip): device time between
+// post_host.h -- the host helpers that the ten post-processing units share (api_gapped.hip, api_hspchain.hip, api_stitch.hip,
+// api_chaintrim.hip, api_fill.hip, api_net.hip, api_netsubset.hip, api_netclass.hip, api_lift.hip, api_diff.hip): device time between
 // events, profiled and checked launches, carving a slot buffer, the checked copies to and from the device, malloc-ed arrays for the
 // caller, the resident block as kernel arguments, the checked gap-cost table as its device image, and the trace batches' packing and
 // runs; and through post_checks.h the input rules they share.  Host code only, everything inline or a template.

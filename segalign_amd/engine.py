@@ -52,6 +52,7 @@ C_ABI_SYMBOLS = [
     "sa_net_subset", "sa_free_net_subset",
     "sa_net_classify", "sa_free_net_class",
     "sa_lift_intervals", "sa_free_lift",
+    "sa_diff_alignments", "sa_free_diff",
 ]
 IVL_DTYPE = np.dtype([("query_start", "<u4"), ("len", "<u4")])  # struct Segment, repeat_masker_src/graph.h:32-35
 STRAND_PLUS, STRAND_MINUS, STRAND_BOTH = 1, 2, 3
@@ -173,6 +174,26 @@ class StitchStats(C.Structure):
     _fields_ = [("links", C.c_uint64), ("swept", C.c_uint64), ("long_links", C.c_uint64), ("dead_links", C.c_uint64),
                 ("low_links", C.c_uint64), ("cells", C.c_uint64), ("records", C.c_uint64), ("member_ms", C.c_double),
                 ("sweep_ms", C.c_double), ("walk_ms", C.c_double), ("trace_bytes", C.c_uint64), ("batches", C.c_uint64)]
+
+
+DIFF_SPAN_DTYPE = np.dtype([("ref_start", "<u4"), ("query_start", "<u4"), ("op_offset", "<u8"), ("n_ops", "<u4"), ("pad", "<u4")])  # sa_diff_span
+DIFF_EVENT_DTYPE = np.dtype([("span", "<u4"), ("ref_pos", "<u4"), ("query_pos", "<u4"), ("len", "<u4"), ("column", "<u4"), ("kind", "u1"),
+                             ("tcode", "u1"), ("qcode", "u1"), ("pad", "u1")])  # sa_diff_event
+DIFF_SUMMARY_DTYPE = np.dtype([("first_event", "<u8"), ("n_events", "<u4"), ("columns", "<u4"), ("matches", "<u4"), ("transitions", "<u4"),
+                               ("transversions", "<u4"), ("others", "<u4"), ("ins_runs", "<u4"), ("ins_bases", "<u4"), ("del_runs", "<u4"),
+                               ("del_bases", "<u4")])  # sa_diff_summary
+DIFF_PER_BASE, DIFF_NO_EVENTS = 1, 2
+DIFF_SUB, DIFF_OTHER, DIFF_INS, DIFF_DEL = 0, 1, 2, 3
+DIFF_NO_CODE = 8
+
+
+class DiffParams(C.Structure):  # sa_diff_params
+    _fields_ = [("flags", C.c_uint32), ("chunk", C.c_uint32)]
+
+
+class DiffStats(C.Structure):  # sa_diff_stats
+    _fields_ = [("spans", C.c_uint64), ("ops", C.c_uint64), ("columns", C.c_uint64), ("work_items", C.c_uint64), ("events", C.c_uint64),
+                ("pairs", C.c_uint64 * 64), ("prep_ms", C.c_float), ("count_ms", C.c_float), ("emit_ms", C.c_float), ("pad", C.c_float)]
 
 
 NET_FILL_DTYPE = np.dtype([("group", "<u4"), ("chain", "<u4"), ("parent", "<i4"), ("depth", "<u4"), ("start", "<u4"), ("end", "<u4"),
@@ -447,6 +468,10 @@ def lib():
                                    C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
                                    C.POINTER(C.c_size_t), C.POINTER(StitchStats)]
     L.sa_free_stitch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sa_diff_alignments.restype = C.c_size_t
+    L.sa_diff_alignments.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(DiffParams),
+                                     C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(DiffStats)]
+    L.sa_free_diff.argtypes = [C.c_void_p, C.c_void_p]
     L.sa_net_chains.restype = C.c_size_t
     L.sa_net_chains.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(NetParams),
                                 C.POINTER(C.c_void_p), C.POINTER(NetStats)]
@@ -932,6 +957,38 @@ def StitchChains(hsps, members, first, rev, buffer=0, gap_open=400, gap_extend=3
     res_l = _chain_take(lnk, n_links.value, STITCH_LINK_DTYPE)
     lib().sa_free_stitch(rec, ops, lnk)
     return (res_r, res_o, res_l, _flat(st)) if links else (res_r, res_o, _flat(st))
+
+
+def diff_spans(records, paths=None):
+    """The alignments of a producer as DiffAlignments takes them, over the producer's ops: GappedAlign / GappedAlignGreedy records with
+    their paths (n_ops = n_left + n_right), or StitchChains records alone.  -> DIFF_SPAN_DTYPE spans."""
+    r = np.asarray(records)
+    src = r if paths is None else np.asarray(paths)
+    if src.shape != r.shape:
+        raise ValueError("paths: one per record")
+    sp = np.zeros(r.size, dtype=DIFF_SPAN_DTYPE)
+    sp["ref_start"], sp["query_start"], sp["op_offset"] = r["ref_start"], r["query_start"], src["op_offset"]
+    sp["n_ops"] = src["n_ops"] if paths is None else src["n_left"] + src["n_right"]
+    return sp
+
+
+def DiffAlignments(spans, ops, rev, buffer=0, per_base=False, events=True, chunk=0):
+    """Where alignments differ from the two resident sequences, what each is made of, and the pair counts of their aligned columns
+    (sa_diff_alignments; contract in include/segalign_amd.h).  spans: DIFF_SPAN_DTYPE (see diff_spans) over ops, uint32
+    (run << 2) | op on strand `rev` of query `buffer`; per_base: every substitution column is its own event; events=False: summaries
+    and statistics only.  -> (DIFF_EVENT_DTYPE events, DIFF_SUMMARY_DTYPE summaries, stats dict; stats["pairs"] is a uint64 array of 64
+    counts by tcode * 8 + qcode)."""
+    sp = np.ascontiguousarray(spans, dtype=DIFF_SPAN_DTYPE)
+    o = np.ascontiguousarray(ops, dtype=np.uint32)
+    p = DiffParams((DIFF_PER_BASE if per_base else 0) | (0 if events else DIFF_NO_EVENTS), int(chunk))
+    ev, sm, st = C.c_void_p(), C.c_void_p(), DiffStats()
+    n = lib().sa_diff_alignments(sp.ctypes.data if sp.size else None, sp.size, o.ctypes.data if o.size else None, o.size, int(bool(rev)),
+                                 int(buffer), C.byref(p), C.byref(ev), C.byref(sm), C.byref(st))
+    res_e, res_s = _chain_take(ev, n, DIFF_EVENT_DTYPE), _chain_take(sm, sp.size, DIFF_SUMMARY_DTYPE)
+    lib().sa_free_diff(ev, sm)
+    out = {k: getattr(st, k) for k, _ in DiffStats._fields_ if k not in ("pairs", "pad")}
+    out["pairs"] = np.array(st.pairs[:], dtype=np.uint64)
+    return res_e, res_s, out
 
 
 def net_blocks(hsps, members, first, axis="target"):

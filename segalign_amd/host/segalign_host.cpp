@@ -62,6 +62,8 @@ struct Config {  // src/graph.h:32-76 with the defaults of src/main.cpp:61-124
     bool gpu_stitch = false;  // --gpu_stitch[=max_link] (with --gpu_chain or --gpu_chain_all): a .stitched.maf file next to every .chain / .chains file (sa_stitch_chains)
     uint32_t stitch_max_link = 0;  // sa_stitch_params.max_link; 0: the engine's default
     bool stitch_min_set = false;
+    bool gpu_diff = false;    // --gpu_diff[=base] (with --gpu_maf or --gpu_stitch): a .diff file next to every .maf / .stitched.maf / .net.maf file (sa_diff_alignments)
+    bool diff_per_base = false;  // --gpu_diff=base: SA_DIFF_PER_BASE
     int stitch_min = INT32_MIN;    // --gpu_stitch_min=N: sa_stitch_params.min_link_score
     bool gpu_net = false;     // --gpu_net[=min_space] (with --gpu_chain_all): a .net file next to every .chains file (sa_net_chains on the target axis)
     uint32_t net_space = 0;   // sa_net_params.min_space; 0: the engine's default
@@ -317,6 +319,35 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
         if (!rev) for (size_t i = 0; i < v.size(); i++) emit(v[i]);
         else for (size_t i = v.size(); i-- > 0;) emit(v[i]);  // :130: reverse vector order on the minus strand
         fclose(f);
+        // with --gpu_diff: the differences of a .maf file's alignments into the file dname, in the .maf file's order:
+        // the spans in their order, or backwards
+        auto write_diff = [&](const std::string& dname, const std::vector<sa_diff_span>& spans, const uint32_t* dops, size_t n_dops, bool backwards) {
+            const sa_diff_params dp = {cfg.diff_per_base ? SA_DIFF_PER_BASE : 0u, 0};
+            sa_diff_event* ev = nullptr;
+            sa_diff_summary* sm = nullptr;
+            sa_diff_alignments(spans.data(), spans.size(), dops, n_dops, rev, buffer, &dp, &ev, &sm, nullptr);
+            FILE* df = fopen((cfg.outdir + "/" + dname).c_str(), "w");
+            if (!df) die(7, "cant open file: %s", dname.c_str());
+            const std::string& qbuf = rev ? Qrc : Q.buf;
+            static const char* const kind_name[4] = {"sub", "other", "ins", "del"};
+            for (size_t x = 0; x < spans.size(); x++) {
+                const size_t k = backwards ? spans.size() - 1 - x : x;
+                const sa_diff_summary& m = sm[k];
+                const size_t r0 = spans[k].ref_start + r_block_start, q0 = spans[k].query_start + q_block_start;
+                const size_t ri = chr_of(R.chr_start, r0), qi = chr_of(qs, q0);
+                fprintf(df, "#a %zu %s %zu %s %c %zu columns=%u matches=%u transitions=%u transversions=%u others=%u ins=%u/%u del=%u/%u events=%u identity=%u/%u\n",
+                        x, R.chr_name[ri].c_str(), r0 - R.chr_start[ri], qn[qi].c_str(), rev ? '-' : '+', q0 - qs[qi], m.columns, m.matches,
+                        m.transitions, m.transversions, m.others, m.ins_runs, m.ins_bases, m.del_runs, m.del_bases, m.n_events, m.matches, m.columns);
+                for (uint64_t e = m.first_event; e < m.first_event + m.n_events; e++) {
+                    const sa_diff_event& d = ev[e];
+                    const size_t r = d.ref_pos + r_block_start, q = d.query_pos + q_block_start;
+                    fprintf(df, "%s\t%s\t%zu\t%s\t%c\t%zu\t%u\t%c\t%c\n", kind_name[d.kind], R.chr_name[ri].c_str(), r - R.chr_start[ri], qn[qi].c_str(),
+                            rev ? '-' : '+', q - qs[qi], d.len, d.kind == SA_DIFF_INS ? '-' : R.buf[r], d.kind == SA_DIFF_DEL ? '-' : qbuf[q]);
+                }
+            }
+            fclose(df);
+            sa_free_diff(ev, sm);
+        };
         std::vector<sa_segment_pair> kept;  // with --gpu_chain or --gpu_chain_all: the chains' HSPs in their order within v
         if (cfg.gpu_chain || cfg.gpu_chain_all) {  // chains within every (target record, query record) pair of this file, DESIGN.md 15 and 16
             const char* flag = cfg.gpu_chain ? "--gpu_chain" : "--gpu_chain_all";
@@ -468,6 +499,11 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
                             qa.c_str());
                 }
                 fclose(sf);
+                if (cfg.gpu_diff) {
+                    std::vector<sa_diff_span> spans(ns);
+                    for (size_t k = 0; k < ns; k++) spans[k] = {sr[k].ref_start, sr[k].query_start, sr[k].op_offset, sr[k].n_ops, 0};
+                    write_diff(sname.substr(0, sname.size() - 3) + "diff", spans, sops, n_sops, false);
+                }
                 sa_free_stitch(sr, sops, nullptr);
             };
             if (cfg.gpu_stitch) write_stitched(base + ".stitched.maf", cv.data(), cv.size(), idx.data(), cfirst.data(), cfirst.size() - 1);
@@ -686,6 +722,11 @@ static void print_segments(int r_block_index, int q_block_index, size_t r_block_
                 if (!rev) for (size_t k = 0; k < na; k++) emit_maf(k);
                 else for (size_t k = na; k-- > 0;) emit_maf(k);  // the .gapped file's order
                 fclose(mf);
+                if (cfg.gpu_diff) {
+                    std::vector<sa_diff_span> spans(na);
+                    for (size_t k = 0; k < na; k++) spans[k] = {al[k].ref_start, al[k].query_start, paths[k].op_offset, paths[k].n_left + paths[k].n_right, 0};
+                    write_diff(base + ".diff", spans, ops, n_ops, rev != 0);
+                }
             }
             if (with_paths) sa_free_gapped_align(al, paths, ops);
             else sa_free_gapped(al);
@@ -751,6 +792,11 @@ static void usage() {
             "  --gpu_stitch[=max_link] (with --gpu_chain or --gpu_chain_all: a .stitched.maf file next to each .chain / .chains file with every\n"
             "      chain as one alignment through all its members, the stretch between two members aligned globally with --gap=O,E; a chain\n"
             "      is cut where a side of that stretch exceeds max_link (default and at most 2048) or holds a record boundary)\n"
+            "  --gpu_diff[=base] (with --gpu_maf or --gpu_stitch: a .diff file next to each .maf, .stitched.maf and .net.maf file: per alignment a\n"
+            "      line '#a <k> <tname> <tstart> <qname> <+|-> <qstart> columns= matches= transitions= transversions= others= ins=<runs>/<bases>\n"
+            "      del=<runs>/<bases> events= identity=<matches>/<columns>', then per difference '<sub|other|ins|del> <tname> <tstart> <qname>\n"
+            "      <+|-> <qstart> <length> <tbase> <qbase>', starts 0-based within the record, '-' for the base a gap lacks; =base: one line per\n"
+            "      substituted base instead of one per run)\n"
             "  --gpu_stitch_min=N (with --gpu_stitch: a chain is also cut at a stretch whose alignment scores less than N)\n"
             "  --gpu_net[=min_space] (with --gpu_chain_all: a .net file next to each .chains file: the kept chains of every target record laid\n"
             "      on the target best first, each filling what is still open, the gaps inside a fill open to lower chains one level down; a\n"
@@ -929,6 +975,11 @@ int main(int argc, char** argv) {
             cfg.gpu_stitch = true;
             cfg.stitch_max_link = (uint32_t)ml;
         }
+        else if (!strcmp(a, "--gpu_diff")) cfg.gpu_diff = true;
+        else if (opt(a, "--gpu_diff", v)) {
+            if (v != "base") { fprintf(stderr, "bad --gpu_diff=%s (base, or no value)\n", v.c_str()); return 1; }
+            cfg.gpu_diff = cfg.diff_per_base = true;
+        }
         else if (opt(a, "--gpu_stitch_min", v)) {
             char* endp = nullptr;
             const long long ms = strtoll(v.c_str(), &endp, 10);
@@ -997,6 +1048,7 @@ int main(int argc, char** argv) {
     if (cfg.chain_fill && !cfg.gpu_chain && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_chain_fill needs --gpu_chain or --gpu_chain_all\n"); return 1; }
     if (cfg.fill_side_set && !cfg.chain_fill) { fprintf(stderr, "--gpu_chain_fill_side needs --gpu_chain_fill\n"); return 1; }
     if (cfg.gpu_stitch && !cfg.gpu_chain && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_stitch needs --gpu_chain or --gpu_chain_all\n"); return 1; }
+    if (cfg.gpu_diff && !cfg.gpu_maf && !cfg.gpu_stitch) { fprintf(stderr, "--gpu_diff needs --gpu_maf or --gpu_stitch\n"); return 1; }
     if (cfg.stitch_min_set && !cfg.gpu_stitch) { fprintf(stderr, "--gpu_stitch_min needs --gpu_stitch\n"); return 1; }
     if (cfg.gpu_net && !cfg.gpu_chain_all) { fprintf(stderr, "--gpu_net needs --gpu_chain_all\n"); return 1; }
     if (cfg.gpu_net_subset && !cfg.gpu_net) { fprintf(stderr, "--gpu_net_subset needs --gpu_net and --gpu_chain_all\n"); return 1; }

@@ -203,6 +203,47 @@ def kept_fields(kept, repeat, align, greedy, prefix):
     return out
 
 
+DIFF = False  # --diff: also read the alignments of --align and --stitch back (sa_diff_alignments)
+
+
+def diff_fields(prefix, spans, ops, repeat, beside):
+    """sa_diff_alignments on a producer's alignments, the run with the least count and emit time, checked against the
+    model.  beside: the producer's own times of the same run, repeated here.  The bytes are what the two passes read of the sequences
+    (two bytes per M column, one per gap column, each pass), over their time, as a fraction of the HBM rate."""
+    if os.path.join(ROOT, "tests") not in sys.path:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import diff_model as D
+    best = None
+    for _ in range(repeat):
+        t0 = time.perf_counter()
+        r = E.DiffAlignments(spans, ops, False, 0)
+        wall = (time.perf_counter() - t0) * 1e3
+        if best is None or r[2]["count_ms"] + r[2]["emit_ms"] < best[0][2]["count_ms"] + best[0][2]["emit_ms"]:
+            best = (r, wall)
+    (ev, sm, st), wall = best
+    t0 = time.perf_counter()
+    want = D.diff(E.copy_ref_codes(), E.copy_query_codes(0, False), spans, ops)
+    model_s = time.perf_counter() - t0
+    if not (np.array_equal(ev, want[0]) and np.array_equal(sm, want[1]) and np.array_equal(st["pairs"], want[2])):
+        raise SystemExit("sa_diff_alignments differs from the model")
+    m_cols = int(st["pairs"].sum())
+    read = 2 * (2 * m_cols + (int(st["columns"]) - m_cols))
+    ms = st["count_ms"] + st["emit_ms"]
+    out = {"spans": int(st["spans"]), "ops": int(st["ops"]), "columns": int(st["columns"]), "work_items": int(st["work_items"]),
+           "events": int(st["events"]), "matches": int(sm["matches"].astype(np.int64).sum()),
+           "transitions": int(sm["transitions"].astype(np.int64).sum()), "transversions": int(sm["transversions"].astype(np.int64).sum()),
+           "others": int(sm["others"].astype(np.int64).sum()), "prep_ms": round(st["prep_ms"], 3), "count_ms": round(st["count_ms"], 3),
+           "emit_ms": round(st["emit_ms"], 3), "call_ms": round(wall, 3), "sequence_bytes_read": read,
+           "fraction_of_hbm_rate": round(read / (ms * 1e-3) / HBM_BYTES_PER_S, 5) if ms > 0 else None, "model_checked": True,
+           "model_s": round(model_s, 1)}
+    out = {prefix + "diff_" + k: v for k, v in out.items()}
+    out.update({prefix + "diff_beside_" + k: round(v, 3) for k, v in beside.items()})
+    return out
+
+
+HBM_BYTES_PER_S = 8e12  # MI355X: 8 TB/s
+
+
 def stitch_fields(hsps, members, repeat, max_link):
     """sa_stitch_chains on the kept chains, the run with the least sweep time, checked against the model."""
     import stitch_model as S
@@ -223,7 +264,8 @@ def stitch_fields(hsps, members, repeat, max_link):
     swept = links[(links["flags"] & E.STITCH_LONG) == 0]
     by_k = {str(k): int(np.count_nonzero([S.instance(int(d)) == k for d in swept["dt"]])) for k in S.INSTANCES}
     grecs = E.GappedExtend(hsps[np.sort(members["hsp_index"])], False, 0, **KW)[0]
-    return {"stitch_max_link": int(max_link or S.MAX_LINK), "stitch_chains": int(first.size - 1), "stitch_members": int(mem.size),
+    extra = diff_fields("stitch_", E.diff_spans(recs), ops, repeat, {"sweep_ms": st["sweep_ms"], "walk_ms": st["walk_ms"]}) if DIFF else {}
+    return {**extra, "stitch_max_link": int(max_link or S.MAX_LINK), "stitch_chains": int(first.size - 1), "stitch_members": int(mem.size),
             "stitch_links": int(st["links"]), "stitch_swept": int(st["swept"]), "stitch_links_by_instance": by_k,
             "stitch_long": int(st["long_links"]), "stitch_dead": int(st["dead_links"]), "stitch_low": int(st["low_links"]),
             "stitch_records": int(st["records"]), "stitch_cells": int(st["cells"]), "stitch_member_ms": round(st["member_ms"], 3),
@@ -585,14 +627,16 @@ def run(name, repeat, align=False, greedy=False, with_sel=True, pieces=0, chain=
             awall = (time.perf_counter() - t0) * 1e3
             total = ast["kernel_ms"] + ast["trace_ms"] + ast["walk_ms"]
             if best_a is None or total < best_a[0]:
-                best_a = (total, arecs, ops, ast, awall)
-        total, arecs, ops, ast, awall = best_a
+                best_a = (total, arecs, ops, ast, awall, paths)
+        total, arecs, ops, ast, awall, paths = best_a
         if not np.array_equal(arecs, recs):
             raise SystemExit("sa_gapped_align returned other records than sa_gapped_extend")
         extra.update({"align_extend_ms": round(ast["kernel_ms"], 3), "align_trace_ms": round(ast["trace_ms"], 3),
                  "align_walk_ms": round(ast["walk_ms"], 3), "align_kernel_ms": round(total, 3), "align_call_ms": round(awall, 3),
                  "align_over_extend": round(total / st["kernel_ms"], 3) if st["kernel_ms"] > 0 else None,
                  "trace_bytes": int(ast["trace_bytes"]), "trace_batches": int(ast["trace_batches"]), "ops": int(ops.size)})
+        if DIFF:
+            extra.update(diff_fields("align_", E.diff_spans(arecs, paths), ops, repeat, {"trace_ms": ast["trace_ms"], "walk_ms": ast["walk_ms"]}))
     if greedy:
         extra.update(greedy_fields(hsps, repeat, with_sel))
     if chain is not None:
@@ -637,7 +681,12 @@ def main():
                     help="also lift N intervals of the target through the sub-chains and through all chains (sa_lift_intervals); implies --net-subset")
     ap.add_argument("--fill", action="store_true", help="also fill the links of the kept chains (sa_fill_chains); implies --chain-all")
     ap.add_argument("--fill-thresh", type=int, default=3000, help="with --fill: thresh")
+    ap.add_argument("--diff", action="store_true", help="with --align and/or --stitch: also read their alignments back (sa_diff_alignments)")
     a = ap.parse_args()
+    if a.diff and not (a.align or a.stitch):
+        ap.error("--diff needs --align or --stitch")
+    global DIFF
+    DIFF = a.diff
     if a.lift < 0 or a.lift > 1 << 26:
         ap.error("--lift takes 1 .. 1 << 26 intervals")
     a.net_subset = a.net_subset or a.lift > 0
