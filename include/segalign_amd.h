@@ -187,7 +187,10 @@ typedef struct sa_interval {
 size_t sa_rm_mask_interval(uint32_t start_pos, uint32_t end_pos, uint32_t ref_start, uint32_t ref_end, int strands, uint32_t M,
                            sa_interval** out, uint64_t* totals /* [3] or NULL */);
 /* The counting + run extraction alone (seeder.cpp:153-188) for a host that keeps the reference's chunk loop and
- * hands over the HSPs it collected for one interval (headers already removed). */
+ * hands over the HSPs it collected for one interval (headers already removed).  An HSP that runs past the end of the block (the
+ * reference indexes out of bounds there) is clipped to it: one with query_start < block_len counts the positions
+ * query_start .. min(query_start + len, block_len) - 1, one that starts at or past block_len counts nothing.  A run that covers the
+ * block's last position is never closed and therefore not returned, as in the reference. */
 size_t sa_rm_coverage_intervals(const sa_segment_pair* hsps, size_t num_hsps, uint32_t block_len, uint32_t M, sa_interval** out);
 void sa_free_intervals(sa_interval* p);
 
@@ -556,6 +559,17 @@ size_t sa_order_hsps(const sa_segment_pair* in, size_t n, int rm, int path, sa_s
 size_t sa_order_hsps_segs(const sa_segment_pair* in, const uint32_t* seg, size_t n, uint32_t nsegs, int rm, int path, uint32_t threads,
                           uint32_t seg_max, int count_on_device, sa_segment_pair** out, uint32_t** out_seg, uint32_t* seg_counts,
                           int* refused);
+
+/* Test entry: the exclusive prefix scan every stage shares (hit prefixes, the table builds, the seeder's flags, tile counts, coverage runs,
+ * the post-processing entries), alone, on `n` uint32 counts of the host's: out[i] = counts[0] + ... + counts[i-1], out[n] = the total, as
+ * n + 1 values of `width` bits -- 32: the sums modulo 2^32, 64: exact.  The scan reads its input at a 256-byte-aligned allocation plus
+ * `skew` words (0..7; the kernel picks a 16-byte or a scalar load by that address), gets exactly the scratch the engine's own callers
+ * size for n counts, pre-filled with a non-zero pattern, and writes into n + 1 values; a guard region of a known byte pattern lies
+ * directly behind the scratch and behind the output.  `out` is the caller's (n + 1 values of `width` bits); intact[3], the caller's:
+ * the scratch's guard, the output's guard and the input were unchanged after the scan (1) or not (0).  Needs sa_initialize_interface
+ * only.  Returns 0.  A skew above 7, a width other than 32 or 64, or n >= 2^31 ends the process with a message and exit code 1.  Held
+ * against numpy.cumsum in tests/test_gpu_scan.py. */
+int sa_scan_counts(const uint32_t* counts, size_t n, uint32_t skew, int width, void* out, uint32_t* intact);
 
 /* ---- gapped extension of HSP anchors (additive) ------------------------------------------------
  *

@@ -478,4 +478,62 @@ size_t sa_order_hsps_segs(const sa_segment_pair* in, const uint32_t* seg, size_t
     return m;
 }
 
+// The prefix scan alone (scan.hip: reduce, scan of the tile sums, downsweep) on `n` counts the host hands in.  The scan's `in` is a
+// 256-byte-aligned allocation plus `skew` words (0..7: which of load_tile's two loads runs is the caller's pointer's choice), its scratch
+// exactly scan_temp_bytes(n) bytes and its output n + 1 values of `width` bits (32: launch_exclusive_scan_u32, 64: _u64), each followed
+// directly by SCAN_GUARD bytes of a known pattern; the scratch holds a non-zero pattern on entry, so a partial the kernels do not write
+// cannot pass for a zero.  One scan runs, in a slot taken as sa_net_chains takes one (InitializeInterface is enough).  out: the caller's
+// n + 1 values of `width` bits; intact[0..2]: the guard behind the scratch, the guard behind the output and the input (with the skew
+// words in front of it) came back as they were written, 1 or 0.  Test entry (tests/test_gpu_scan.py holds it to numpy.cumsum): own
+// buffers, no kernel of its own, the guards are compared on the host.  A skew above 7, a width other than 32 / 64 or n >= 2^31 ends the
+// process with a message and exit code 1.
+int sa_scan_counts(const uint32_t* counts, size_t n, uint32_t skew, int width, void* out, uint32_t* intact) {
+    require_init("sa_scan_counts");
+    if (skew > 7 || (width != 32 && width != 64) || n > 0x7FFFFFFFull) {
+        fprintf(stderr, "Error: sa_scan_counts: skew %u (0..7), width %d (32 or 64) or %zu counts (below 2^31) out of range\n", skew, width, n);
+        exit(1);
+    }
+    constexpr size_t SCAN_GUARD = 4096;
+    constexpr int PAT_SKEW = 0x3C, PAT_TEMP = 0xA5, PAT_OUT = 0xE7, PAT_GUARD = 0x5C;
+    const size_t in_bytes = ((size_t)skew + n) * sizeof(uint32_t), temp_bytes = scan_temp_bytes(n), out_bytes = (n + 1) * (size_t)(width / 8);
+    Slot* sl = acquire_slot_early();
+    hipStream_t st = sl->stream;
+    uint8_t *d_in = nullptr, *d_temp = nullptr, *d_out = nullptr;
+    check_memcpy(hipMalloc((void**)&d_in, std::max<size_t>(in_bytes, 256)), "scan counts: input");
+    check_memcpy(hipMalloc((void**)&d_temp, temp_bytes + SCAN_GUARD), "scan counts: scratch");
+    check_memcpy(hipMalloc((void**)&d_out, out_bytes + SCAN_GUARD), "scan counts: output");
+    if ((reinterpret_cast<uintptr_t>(d_in) & 255) != 0) {
+        fprintf(stderr, "Error: sa_scan_counts: the input allocation is not 256-byte aligned\n");
+        exit(15);
+    }
+    std::vector<uint32_t> h_in((size_t)skew + n, 0x01010101u * PAT_SKEW), back_in(h_in.size());  // (the skew words keep the pattern)
+    if (n) memcpy(h_in.data() + skew, counts, n * sizeof(uint32_t));
+    if (in_bytes) check_memcpy(hipMemcpyAsync(d_in, h_in.data(), in_bytes, hipMemcpyHostToDevice, st), "scan counts: upload");
+    check_memcpy(hipMemsetAsync(d_temp, PAT_TEMP, temp_bytes, st), "scan counts: scratch pattern");
+    check_memcpy(hipMemsetAsync(d_temp + temp_bytes, PAT_GUARD, SCAN_GUARD, st), "scan counts: scratch guard");
+    check_memcpy(hipMemsetAsync(d_out, PAT_OUT, out_bytes, st), "scan counts: output pattern");
+    check_memcpy(hipMemsetAsync(d_out + out_bytes, PAT_GUARD, SCAN_GUARD, st), "scan counts: output guard");
+    const uint32_t* in = reinterpret_cast<const uint32_t*>(d_in) + skew;
+    if (width == 32) launch_exclusive_scan_u32(in, reinterpret_cast<uint32_t*>(d_out), n, d_temp, st);
+    else launch_exclusive_scan_u64(in, reinterpret_cast<uint64_t*>(d_out), n, d_temp, st);
+    check_launch("scan counts");
+    std::vector<uint8_t> g_temp(SCAN_GUARD), g_out(SCAN_GUARD);
+    check_memcpy(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st), "scan counts: download");
+    check_memcpy(hipMemcpyAsync(g_temp.data(), d_temp + temp_bytes, SCAN_GUARD, hipMemcpyDeviceToHost, st), "scan counts: scratch guard");
+    check_memcpy(hipMemcpyAsync(g_out.data(), d_out + out_bytes, SCAN_GUARD, hipMemcpyDeviceToHost, st), "scan counts: output guard");
+    if (in_bytes) check_memcpy(hipMemcpyAsync(back_in.data(), d_in, in_bytes, hipMemcpyDeviceToHost, st), "scan counts: input back");
+    check_sync(st, "scan counts");
+    auto all_guard = [&](const std::vector<uint8_t>& g) {
+        for (uint8_t b : g)
+            if (b != (uint8_t)PAT_GUARD) return 0u;
+        return 1u;
+    };
+    intact[0] = all_guard(g_temp);
+    intact[1] = all_guard(g_out);
+    intact[2] = back_in == h_in ? 1u : 0u;
+    (void)hipFree(d_in); (void)hipFree(d_temp); (void)hipFree(d_out);
+    release_slot(sl);
+    return 0;
+}
+
 }  // extern "C"

@@ -10,14 +10,17 @@
 //   * `len` is bases-1, so an HSP covers query_start .. query_start+len-1 (its last base is not counted);
 //   * a run is emitted when the first uncovered position AFTER it is seen (:177-184), so a run that reaches the end
 //     of the block is never written: the host drops a last run that ends at block_len (api_rm.hip coverage_finish; only
-//     HSPs with query_start + len == block_len make one); with M == 0 the whole block is one unterminated run and nothing is written.
+//     HSPs with query_start + len >= block_len make one); with M == 0 the whole block is one unterminated run and nothing is written.
+// The project's own rule where the reference indexes out of bounds (include/segalign_amd.h, sa_rm_coverage_intervals):
+//   * an HSP that runs past the end of the block is CLIPPED to it: one with query_start < block_len counts
+//     query_start .. min(query_start + len, block_len) - 1, one that starts at or past block_len counts nothing.
 #include "kernels.h"
 
 namespace sa {
 
 constexpr int COV_THREADS = 256;
 
-// diff[query_start] += 1, diff[query_start+len] -= 1 ; range[0] = min start, range[1] = max end (atomic)
+// diff[query_start] += 1, diff[min(query_start+len, block_len)] -= 1 ; range[0] = min start, range[1] = max clipped end (atomic)
 template <typename Rec>
 __global__ __launch_bounds__(COV_THREADS) void coverage_add_kernel(const Rec* __restrict__ hsps, uint32_t n,
                                                                    uint32_t* __restrict__ diff, uint32_t diff_len,
@@ -26,12 +29,13 @@ __global__ __launch_bounds__(COV_THREADS) void coverage_add_kernel(const Rec* __
     uint32_t lo = 0xFFFFFFFFu, hi = 0u;
     if (i < n) {
         const uint32_t qs = hsps[i].query_start, len = hsps[i].len;
-        const uint64_t e = (uint64_t)qs + len;
-        if (len > 0 && e < diff_len) {  // e <= block_len always holds for an HSP inside the block (diff_len = block_len+1)
+        const uint32_t block_len = diff_len - 1;  // callers pass block_len + 1 words (one behind the block for an end at block_len): block_len < 2^32 - 1
+        if (len > 0 && qs < block_len) {
+            const uint32_t e = (uint32_t)min((uint64_t)qs + len, (uint64_t)block_len);  // clipped to the block: qs < e <= block_len
             atomicAdd(&diff[qs], 1u);
             atomicAdd(&diff[e], 0xFFFFFFFFu);
             lo = qs;
-            hi = (uint32_t)e;
+            hi = e;
         }
     }
     // wave-level min/max, one atomic pair per wave

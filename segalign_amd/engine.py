@@ -36,7 +36,7 @@ C_ABI_SYMBOLS = [
     "sa_copy_query_codes", "sa_get_query_len", "sa_device_make_seeds", "sa_version",
     "sa_rm_mask_interval", "sa_rm_coverage_intervals", "sa_free_intervals", "sa_get_filter_mode",
     "sa_seed_interval", "sa_seed_and_filter_chunks", "sa_max_chunks_per_call", "sa_get_chunks_per_call", "sa_extend_hits", "sa_order_hsps",
-    "sa_order_hsps_segs",
+    "sa_order_hsps_segs", "sa_scan_counts",
     "sa_get_lookup_mode", "sa_get_neighbourhood_entries",
     "sa_get_table_build_info", "sa_copy_neighbourhood_starts", "sa_copy_neighbourhood_records",
     "sa_probe_call", "sa_free_probe_call",
@@ -380,6 +380,8 @@ def lib():
     L.sa_order_hsps_segs.restype = C.c_size_t
     L.sa_order_hsps_segs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int,
                                      C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_int)]
+    L.sa_scan_counts.restype = C.c_int
+    L.sa_scan_counts.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
     L.sa_extend_hits.restype = C.c_size_t
     L.sa_extend_hits.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]
     L.sa_get_neighbourhood_entries.restype = C.c_uint64
@@ -676,6 +678,16 @@ def OrderHspsSegs(records, seg, nsegs, rm=False, path=1, threads=0, seg_max=0, c
     lib().sa_free_segments(out)
     lib().sa_free_segments(oseg)
     return res, rseg, counts, bool(refused.value)
+
+
+def ScanCounts(counts, skew=0, width=32):
+    """The exclusive prefix scan alone on uint32 `counts`, read at a 256-byte-aligned address plus `skew` words (sa_scan_counts; test entry).
+    -> (the n + 1 sums as uint32 or uint64, dict(temp_guard, out_guard, input): each True when it came back unchanged)"""
+    c = np.ascontiguousarray(counts, dtype=np.uint32)
+    out = np.zeros(c.size + 1, dtype=np.uint64 if int(width) == 64 else np.uint32)
+    intact = np.zeros(3, dtype=np.uint32)
+    lib().sa_scan_counts(c.ctypes.data if c.size else None, c.size, int(skew), int(width), out.ctypes.data, intact.ctypes.data)
+    return out, dict(temp_guard=bool(intact[0]), out_guard=bool(intact[1]), input=bool(intact[2]))
 
 
 def ExtendHits(hits, rev, buffer):

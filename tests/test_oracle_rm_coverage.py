@@ -3,29 +3,7 @@ an independent numpy model, and the interval plan (repeat_masker_src/main.cpp:31
 import numpy as np
 import pytest
 
-
-def numpy_model(hsps, block_len, M):
-    """difference array + cumsum, uint8 wrap, runs closed only by a following uncovered position."""
-    d = np.zeros(block_len + 1, dtype=np.int64)
-    for h in hsps:
-        if h["len"] > 0:
-            d[h["query_start"]] += 1
-            d[h["query_start"] + h["len"]] -= 1
-    depth = (np.cumsum(d)[:block_len] & 0xFF).astype(np.int64)
-    cov = depth >= M
-    out = []
-    i = 0
-    while i < block_len:
-        if cov[i]:
-            j = i
-            while j < block_len and cov[j]:
-                j += 1
-            if j < block_len:  # no flush after the loop (:168-186)
-                out.append((i, j - i))
-            i = j
-        else:
-            i += 1
-    return out
+from coverage_model import numpy_model
 
 
 def random_hsps(O, rng, n, block_len, max_len):
