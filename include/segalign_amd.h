@@ -94,9 +94,12 @@ void sa_clear_query(uint32_t buffer);
 /* ---- the hot call ---------------------------------------------------------------------------------------- */
 
 /* g_SeedAndFilter, src/seed_filter.h:6 ; def src/seed_filter.cu:682-828.
- * seeds[i] = (key << 32) + query_position (src/seeder.cpp:60-61).  A vector that is what src/seeder.cpp:57-74 emits for the
- * positions it spans (checked on the device) is looked up table-direct like sa_seed_and_filter_range; any other vector takes the
- * reference-shaped path (sa_call_stats.lookup_path tells which).  Returns the element count of *out
+ * seeds[i] = (key << 32) + query_position (src/seeder.cpp:60-61).  A vector that EQUALS what src/seeder.cpp:57-74 emits for the
+ * positions [first, last + 1) it spans (first / last: the positions of its first and last word; checked on the device) is looked
+ * up table-direct like sa_seed_and_filter_range(first, last + 1); any other vector -- a word missing, repeated, out of order or
+ * altered, a group at a position where no seed stands -- takes the reference-shaped path on the words as they are.  The result is
+ * the reference's either way; sa_call_stats.lookup_path tells which path it was (tests/test_gpu_dropin_paths.py holds both to a
+ * model, edit by edit; sa_rm_seed_and_filter decides the same way).  Returns the element count of *out
  * (>= 1): out[0] is the header {len = total anchors, score = (int)num_hits} (seed_filter.cu:806-809), followed by
  * the HSPs of each iteration in order.  *out is owned by the caller; release with sa_free_segments. */
 size_t sa_seed_and_filter(const uint64_t* seeds, size_t num_seeds, int rev, uint32_t buffer, sa_segment_pair** out);
@@ -311,7 +314,9 @@ typedef struct sa_call_stats {
     uint32_t num_iter;
     int device;
     int lookup_path;        /* seed lookup path the call took: 0 general (seed words -> buckets -> hit list), 1 table-direct,
-                               2 table-direct with target context (sa_get_lookup_mode) */
+                               2 table-direct with target context (sa_get_lookup_mode).  A drop-in call (host seed vector) reports 1 or
+                               2 -- the lookup mode -- exactly when its vector equals the device seeder's for the positions it spans,
+                               and 0 otherwise */
     uint32_t path_flags;    /* SA_PATH_*: which of the engine's rare branches the call took (diagnostics; the results never depend on them).
                                Summed statistics (sa_seed_calls, sa_seed_interval) carry the OR over their calls */
     uint64_t num_forwarded; /* context-table calls: the records the second level read from the class filter's (level 1's) hand-over list in

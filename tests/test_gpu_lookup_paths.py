@@ -1,7 +1,8 @@
 """GPU: the three seed-lookup paths of the device-seeded entry points give the oracle's result bit for bit:
   2  table-direct with target context (neighbourhood table of 28-byte records, class filter + second level; default)
   1  table-direct, positions only (SEGALIGN_AMD_NO_CTX=1; what a target block too large for the context table gets)
-  0  general path: seed words -> bucket lookup -> hit list (SEGALIGN_AMD_NO_TD=1; also every drop-in call)
+  0  general path: seed words -> bucket lookup -> hit list (SEGALIGN_AMD_NO_TD=1; also a drop-in call whose host vector is not
+     the seeder's own for the positions it spans -- tests/test_gpu_dropin_paths.py)
 src/seed_filter.cu:157-230 + :682-828 (lookup, iteration plan, hits) on every path; repeat-masker variant included."""
 import os
 
